@@ -28,8 +28,17 @@ procedural colour texture: normals + intensity gradients + 6x6 response + the Ha
 `--workload dense`: SURVEY 8(d)'s "dense" data point, the configs[2] pass on the same room scene
 at 10x the point density (10M points, k(0.05) ~ 2,400).
 
+A plain run sets up, warms up, times `--steps` steps and prints the result line (`value`,
+`ms_per_step`, the stage timers of the timed region).  `--full` adds everything that takes runs of
+its own: the per-kernel breakdown and `roofline` (extra steps with per-kernel events, the isolated
+normal stage), the H2D/D2H-inclusive leg, the back-to-back comparison of the batch pipeline, the
+CPU restatement (`cpu_baseline`) and the full-size parity against it; `--no-cpu-baseline` and
+`--no-e2e` drop those two legs of a `--full` run.  `--dump-outputs DIR` writes what the last timed
+step handed to its caller as DIR/<name>.npy, finite throughout: quiet_NaN rows of a float32
+output are written as 0 and flagged in DIR/<name>_valid.npy (dump_outputs).
+
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload fpfh|shot|...] [--scans S]
-                    [--no-cpu-baseline] [--no-e2e]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-e2e]]
 """
 from __future__ import annotations
 
@@ -240,6 +249,42 @@ def load_pmc(name):
     return d
 
 
+DUMP_BUDGET = 60_000_000  # bytes per --dump-outputs directory (the .npy headers included): under 64 MB
+
+
+def dump_outputs(directory, arrays):
+    """`--dump-outputs DIR`: the arrays the last timed step handed to its caller, DIR/<name>.npy
+    each; float32 stays float32, everything else (indices, doubles) becomes float64 (exact for
+    32-bit indices).  Every file holds finite numbers only: a float32 output may carry PCL's
+    quiet_NaN rows (a point without neighbours, a descriptor without a frame), so it is written
+    with those entries as 0 and DIR/<name>_valid.npy (float32, one 1/0 per row: every entry of the
+    row finite) beside it.  Over DUMP_BUDGET in all, every output above 1 MB keeps a fixed, seeded
+    sample of its rows (the same rows in every run of the same arguments, the same in <name> and
+    <name>_valid), sized so that the directory fits the budget."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    units = {}  # name -> the files of one output: [(file name, array)], rows aligned
+    for nm, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype == np.float32:
+            finite = np.isfinite(a)
+            units[nm] = [(nm, np.ascontiguousarray(np.where(finite, a, np.float32(0)))),
+                         (nm + "_valid", finite.reshape(len(a), -1).all(1).astype(np.float32))]
+        else:
+            units[nm] = [(nm, np.ascontiguousarray(a, dtype=np.float64))]
+    size = {nm: sum(a.nbytes for _, a in files) for nm, files in units.items()}
+    big = {nm for nm in units if size[nm] > (1 << 20)}
+    total_big = sum(size[nm] for nm in big)
+    room = DUMP_BUDGET - sum(size[nm] for nm in units if nm not in big) - 256 * sum(len(f) for f in units.values())
+    for nm, files in units.items():
+        pick = None
+        if nm in big and total_big > room:
+            n = len(files[0][1])
+            pick = np.sort(np.random.default_rng(64).choice(n, max(1, int(n * room / total_big)), replace=False))
+        for fname, a in files:
+            np.save(os.path.join(directory, fname + ".npy"), a if pick is None else a[pick])
+
+
 def main():
     if len(sys.argv) == 3 and sys.argv[1] == "--cpu-child":  # (cpu_baseline's pinned child: no torch)
         cpu_child(sys.argv[2])
@@ -256,9 +301,19 @@ def main():
     ap.add_argument("--cycle", type=int, default=4,
                     help="headline (fpfh, one scan per step at --gpus 1): distinct 1M-pt room scans cycled through "
                          "the timed steps (seeds 2, 100, 101, 102), each checked at full size against the oracle")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-buffer (H2D/D2H inside the step) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: per-kernel breakdown and roofline, the H2D/D2H-inclusive leg, the "
+                         "CPU restatement and the full-size parity against it (minutes; off: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32/float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU restatement")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="with --full: skip the host-buffer (H2D/D2H inside the step) leg")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    args.cpu = args.full and not args.no_cpu_baseline
+    args.e2e = args.full and not args.no_e2e
 
     # driver-style `bench.py --gpus N` without an external launcher: start the N ranks as a child
     # torch.distributed.run BEFORE anything here touches a GPU, and exit with its code
@@ -408,7 +463,31 @@ def bench_scans(args, torch, dist, dev, world, rank, local):
         state["rows"] = int(blocks[-1][0].shape[0]) if blocks else 0
         if world > 1 and not shot:
             state["gathered"] = gather_to_root(torch, dist, blocks, 33, dev, per_rank_max)
+        state["blocks"], state["last"] = blocks, (state["i"] - 1) % cycle if cycle > 1 else None
         return blocks
+
+    def last_step_outputs():
+        """What the last timed step handed to its caller (rank 0), for --dump-outputs: per scan the
+        descriptor rows and their cloud indices (at N > 1 the gathered batch, in scan order), the
+        normals + curvature the pass left in the scan's buffers (not in the demand mode, which leaves
+        most of them unwritten), and the NARF keypoints (range-image pixel indices) of a one-scan step."""
+        torch.cuda.synchronize(dev)
+        out = {}
+        if world > 1 and not shot:
+            for i, (d, idx) in enumerate(in_scan_order(state["gathered"], n_scans, world)):
+                out[f"descriptors_scan{i}"], out[f"descriptor_indices_scan{i}"] = d.cpu().numpy(), idx.cpu().numpy()
+            return out
+        done = [scans[state["last"]]] if cycle > 1 else scans
+        for i, (b, (d, idx)) in enumerate(zip(done, state["blocks"])):
+            tag = "" if len(done) == 1 else f"_scan{i}"
+            out["descriptors" + tag] = d.cpu().numpy()
+            if idx is not None:
+                out["descriptor_indices" + tag] = idx.cpu().numpy()
+            if not demand:
+                out["normals" + tag] = torch.stack((b.nx, b.ny, b.nz, b.curv), 1).cpu().numpy()
+        if len(done) == 1 and run_batch is None and state["kp"] is not None:
+            out["keypoints"] = np.asarray(state["kp"])
+        return out
 
     # warm-up; per-scan neighbour counts of the normal estimation (for the algorithmic bytes)
     nb_scan, long_scan = [], []
@@ -418,7 +497,7 @@ def bench_scans(args, torch, dist, dev, world, rank, local):
             for j, b in enumerate(scans):
                 # the neighbour count of the scan, from one exact estimation (the fast mode has no
                 # lists; the support-first schedule's statistics cover its last subset only)
-                if w == 0 and (fast or (run_fpfh.support_first and not demand)):
+                if w == 0 and args.full and (fast or (run_fpfh.support_first and not demand)):
                     ctx_n.normals_dev(b.x, b.y, b.z, 0.05, b.nx, b.ny, b.nz, b.curv)
                     nb_scan.append(ctx_n.stat("normals_neighbors"))
                     long_scan.append((ctx_n.stat("normals_long_neighbors"), ctx_n.stat("normals_long_queries")))
@@ -435,7 +514,7 @@ def bench_scans(args, torch, dist, dev, world, rank, local):
     # the same scans back to back through the single-scan overlapped pass (no cross-scan
     # pipelining), for the batch pipeline's gain; not part of `value`
     seq_ms = None
-    if run_batch is not None and rank == 0:
+    if run_batch is not None and rank == 0 and args.full:
         seq_el = timed(torch, dist, dev, 1, max(1, args.steps // 4), lambda: [one_scan(b) for b in scans])
         seq_ms = seq_el / max(1, args.steps // 4) * 1e3
     # inside the timed region only the stage timers run (one HIP-event pair per stage call: the
@@ -452,12 +531,16 @@ def bench_scans(args, torch, dist, dev, world, rank, local):
     # deferred errors of the stream-ordered calls (FPFH capacity), outside the timed region
     (run_batch or run_fpfh).check()
     timers = read_timers()
-    detail_steps = max(3, args.steps // 4)
-    for c in (ctx, ctx_n):
-        c.set_timing(True)
-        c.reset_timing()
-    timed(torch, dist, dev, world, detail_steps, step)
-    detail = read_timers()
+    if args.dump_outputs and rank == 0:  # before any later leg rewrites the scan buffers
+        dump_outputs(args.dump_outputs, last_step_outputs())
+    detail, detail_steps = None, 0
+    if args.full:
+        detail_steps = max(3, args.steps // 4)
+        for c in (ctx, ctx_n):
+            c.set_timing(True)
+            c.reset_timing()
+        timed(torch, dist, dev, world, detail_steps, step)
+        detail = read_timers()
     for c in (ctx, ctx_n):
         c.set_timing(False)
 
@@ -470,7 +553,9 @@ def bench_scans(args, torch, dist, dev, world, rank, local):
         raise KeyError(nm)
 
     if os.environ.get("PFX_BENCH_VERBOSE"):
-        rep = {nm: round(ms / detail_steps, 3) for nm, (ms, _) in detail.items() if ms > 0}
+        # (--full: every kernel group, from the extra steps; else the stage timers of the timed region)
+        rep = {nm: round(ms / (detail_steps if args.full else args.steps), 3)
+               for nm, (ms, _) in (detail if args.full else timers).items() if ms > 0}
         print("per-step kernel ms:", json.dumps(rep), file=sys.stderr, flush=True)
         stats = {}
         for nm in VERBOSE_STATS:
@@ -494,9 +579,9 @@ def bench_scans(args, torch, dist, dev, world, rank, local):
     # the host-buffer leg (SURVEY 8(d) "H2D/D2H included"): each scan's xyz copied from pinned
     # host memory inside the step, descriptors + indices copied back; reported beside `value`
     e2e = None
-    if not args.no_e2e and not shot and cycle > 1:
+    if args.e2e and not shot and cycle > 1:
         e2e = bench_e2e_pipelined(torch, dist, dev, world, args.steps, host, cycle, npts, one_scan, alloc)
-    elif not args.no_e2e and not shot:
+    elif args.e2e and not shot:
         hx = [[torch.from_numpy(a).pin_memory() for a in h] for h in host]
         hd = [torch.empty((1 << 16, 33), dtype=torch.float32).pin_memory() for _ in scans]
         hi = [torch.empty((1 << 16,), dtype=torch.int32).pin_memory() for _ in scans]
@@ -525,7 +610,7 @@ def bench_scans(args, torch, dist, dev, world, rank, local):
     # `value`): inside the step it shares the CUs with NARF on the other stream
     iso = None
     deviation = None
-    if rank == 0 and fast:  # the fast mode against the product (parity-exact) path on the same scan
+    if rank == 0 and fast and args.full:  # against the product (parity-exact) path on the same scan
         b = scans[0]
         fast_n = [t.clone() for t in (b.nx, b.ny, b.nz, b.curv)]
         fast_d = b.desc[:state["rows"]].clone()
@@ -535,7 +620,8 @@ def bench_scans(args, torch, dist, dev, world, rank, local):
         deviation = fast_deviation(torch, fast_n, fast_d, b, k_exact, np.array_equal(np.asarray(kp_exact),
                                                                                      np.asarray(state["kp"])))
         run_fpfh.fast_normals = True
-    if rank == 0 and not shot and not demand:  # (demand: the full estimation would overwrite the checked normals)
+    # (demand: the full estimation would overwrite the checked normals)
+    if rank == 0 and args.full and not shot and not demand:
         b = scans[0]
         ctx_n.set_timing(True)
         ctx_n.reset_timing()
@@ -546,9 +632,13 @@ def bench_scans(args, torch, dist, dev, world, rank, local):
         ctx_n.set_timing(False)
 
     if rank == 0:
-        line = scans_line(args, world, n_scans, 1 if cycle > 1 else len(mine), shot, elapsed, timers, iso, nb_scan,
-                          long_scan, stat, npts,
-                          fast=fast, detail=detail, detail_steps=detail_steps, demand=demand)
+        scans_here = 1 if cycle > 1 else len(mine)
+        roofline = None
+        if args.full:
+            roofline = scans_roofline(args, scans_here, shot, timers, iso, nb_scan, long_scan, stat, npts,
+                                      fast=fast, detail=detail, detail_steps=detail_steps, demand=demand)
+        line = scans_line(args, world, n_scans, scans_here, shot, elapsed, timers, nb_scan, roofline, npts,
+                          fast=fast, demand=demand)
         if deviation is not None:
             line["deviation_from_parity_path"] = deviation
         if cycle > 1:
@@ -570,12 +660,13 @@ def bench_scans(args, torch, dist, dev, world, rank, local):
             line["config"]["gathered_on_rank0"] = batch
             line["config"]["ranks_seen_by_rccl"] = dist.get_world_size()
             line["config"]["backend"] = dist.get_backend()
-        line["end_to_end_h2d_d2h"] = e2e
+        if args.full:
+            line["end_to_end_h2d_d2h"] = e2e
         cpu = None
         if fast:
             cpu = {"value": None, "note": "see the configs[2] line: the CPU restatement is PCL's path, which this "
                                           "opt-in mode departs from by design"}
-        elif world == 1 and not args.no_cpu_baseline and not dense:
+        elif world == 1 and args.cpu and not dense:
             x, y, z = host[0]
             kp0, rows0 = resident[0] if cycle > 1 else (state["kp"], state["rows"])
             cb = cpu_baseline(x, y, z, "fpfh" if demand else args.workload, sample_np)
@@ -611,7 +702,8 @@ def bench_scans(args, torch, dist, dev, world, rank, local):
         if dense:
             cpu = {"value": None, "note": "not run: the CPU restatement needs ~10 min per pass at this density "
                                           "(normals ~24.6G neighbour terms); see the configs[2] line"}
-        line["cpu_baseline"] = cpu
+        if args.full:
+            line["cpu_baseline"] = cpu
         print(json.dumps(line), flush=True)
     run_fpfh.close()
     if run_batch is not None:
@@ -692,12 +784,10 @@ def fast_deviation(torch, fast_n, fast_d, b, k, same_kp):
     return out
 
 
-def scans_line(args, world, n_scans, scans_here, shot, elapsed, timers, iso, nb_scan, long_scan, stat, npts=N_POINTS,
-               fast=False, detail=None, detail_steps=1, demand=False):
-    """The contract line of bench_scans (rank 0), roofline over the neighbour-gather stage."""
+def scans_roofline(args, scans_here, shot, timers, iso, nb_scan, long_scan, stat, npts=N_POINTS,
+                   fast=False, detail=None, detail_steps=1, demand=False):
+    """--full: the `roofline` of bench_scans' line (rank 0), over the neighbour-gather stage."""
     per_scan_calls = args.steps * scans_here  # scans this rank processes per step
-    ms_per_step = elapsed / args.steps * 1e3
-    value = n_scans * npts * args.steps / elapsed / 1e6
     nb = sum(nb_scan) / len(nb_scan)
     long_nb = sum(l[0] for l in long_scan) / len(long_scan)
     long_q = sum(l[1] for l in long_scan) / len(long_scan)
@@ -757,7 +847,7 @@ def scans_line(args, world, n_scans, scans_here, shot, elapsed, timers, iso, nb_
                                 "kernels_ms": {nm: round(iso[nm], 4) for nm in (("grid_bbox", "grid_build",
                                                                                  "normals_mfma") if fast else parts)},
                                 "note": "pfx_normals_dev alone on the device after the timed region (not `value`)"}
-    if shot:  # configs[3]: k_shot heads the line (the dominant kernel of that step)
+    if shot:  # configs[3]: k_shot heads the roofline (the dominant kernel of that step)
         shot_ms, shot_n = timers["shot"]
         shot_s = (shot_ms / max(shot_n, 1)) / 1e3
         sbytes = stat("shot_neighbors") * 24
@@ -771,6 +861,16 @@ def scans_line(args, world, n_scans, scans_here, shot, elapsed, timers, iso, nb_
                     "algorithmic_bytes_per_launch": int(sbytes), "avg_ms": round(shot_s * 1e3, 4),
                     "note": "sum_q |N_0.08(q)| x 24 B (xyz + normal) per launch (SURVEY 8(d)); VALU/LDS-atomic "
                             "bound, not HBM", "normals_stage": stage}
+    return roofline
+
+
+def scans_line(args, world, n_scans, scans_here, shot, elapsed, timers, nb_scan, roofline, npts=N_POINTS,
+               fast=False, demand=False):
+    """The contract line of bench_scans (rank 0); `roofline` (scans_roofline) with --full."""
+    per_scan_calls = args.steps * scans_here  # scans this rank processes per step
+    ms_per_step = elapsed / args.steps * 1e3
+    value = n_scans * npts * args.steps / elapsed / 1e6
+    if shot:  # configs[3]
         metric = "Mpoints/s through NARF keypoint + normals + SHOT-352 descriptor on 1M-pt underwater-style cloud"
         workload = (f"configs[3] 1M-pt synthetic seabed, NARF(support 0.2) + normals(r 0.05) + SHOT-352(r 0.08) at "
                     f"the keypoints + a fixed {SHOT_SAMPLE}-point sample" + ("" if world == 1 else ", one scan per GPU"))
@@ -801,7 +901,8 @@ def scans_line(args, world, n_scans, scans_here, shot, elapsed, timers, iso, nb_
             metric = "Mpoints/s through NARF keypoint + FPFH descriptor, configs[2] scene at 10x density"
             workload = (f"SURVEY 8(d) dense variant: configs[2]'s room scene (same scale) at {npts // 1_000_000}M "
                         f"points, NARF(support 0.2) + normals(r 0.05) + FPFH(r 0.08) at the keypoints")
-            data = f"synthetic (synth_room at 10x density: {npts} points, k(0.05)~{int(nb / npts)}; see synth.py)"
+            k = int(sum(nb_scan) / len(nb_scan) / npts)  # (neighbour counts of the warm-up's estimations)
+            data = f"synthetic (synth_room at 10x density: {npts} points, k(0.05)~{k}; see synth.py)"
     # the critical path: every stage's HIP-event time on its own stream inside the
     # timed region, per scan -- NARF on the main stream beside the normal estimation on the side
     # stream, then FPFH's SPFH and weighting on the main stream behind the normals
@@ -814,15 +915,17 @@ def scans_line(args, world, n_scans, scans_here, shot, elapsed, timers, iso, nb_
     stages_note = ("HIP events around each stage on its stream, inside the timed region, per scan; NARF (range image, "
                    "borders, interest, NMS + the host greedy selection, keypoint gather) runs on the main stream while "
                    "the normal estimation runs on the side stream, then SPFH and the weighting follow the normals")
-    return {
+    line = {
         "metric": metric, "value": round(value, 4), "unit": "Mpoints/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
         "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": data,
         "config": {"workload": workload, "points_per_scan": npts, "scans_per_step": n_scans,
                    "image": "640x480", "parallelism": f"scan-per-gpu x{world}"},
         "stages_ms_per_scan": stages, "stages_note": stages_note,
-        "roofline": roofline,
     }
+    if roofline is not None:
+        line["roofline"] = roofline
+    return line
 
 
 def bench_match(args, torch, dev, world, rank, local):
@@ -873,6 +976,9 @@ def bench_match(args, torch, dev, world, rank, local):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     ns, nt = len(src), len(tgt)
+    if args.dump_outputs and rank == 0:  # the correspondence list of the last step: (source row, target row)
+        dump_outputs(args.dump_outputs, {"query_indices": q[:npairs].cpu().numpy(),
+                                         "match_indices": m[:npairs].cpu().numpy()})
     if rank == 0:
         # MFMA work per step: one tile pass over the padded (ns x nt) grid, K = 3 x 352 (bf16 split);
         # the candidate test runs over the pruned pair list the pass emits (a second contraction only
@@ -889,7 +995,7 @@ def bench_match(args, torch, dev, world, rank, local):
         tiles_s = (tb + tf + tsd) / max(nb, 1) / 1e3
         achieved = flops / tiles_s / 1e12 if tiles_s > 0 else 0.0
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.cpu:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_lib as O
             threads = int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or (os.cpu_count() or 1)
@@ -968,6 +1074,8 @@ def bench_iss(args, torch, dev, world, rank, local):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"keypoints": idx[:k].cpu().numpy()})
     if rank == 0:
         # the scatter kernel (k_iss_cov): every point's salient neighbours' coordinates and its
         # third value; algorithmic bytes per launch = sum_q |N_6res(q)| x 12 B + N x 8 B
@@ -981,7 +1089,7 @@ def bench_iss(args, torch, dev, world, rank, local):
                              "iss_scatter", "iss_ordered", "iss_nms")}
         res = ctx.cloud_resolution_dev(dx, dy, dz)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.cpu:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_lib as O
             threads = int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or (os.cpu_count() or 1)
@@ -1061,6 +1169,8 @@ def bench_harris(args, torch, dev, world, rank, local, six=False):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"keypoints": idx[:k].cpu().numpy()})
     if rank == 0:
         nb = ctx.stat("normals_neighbors")
         if six:
@@ -1087,7 +1197,7 @@ def bench_harris(args, torch, dev, world, rank, local, six=False):
         stages = {nm: round(ctx.kernel_time(nm)[0] / args.steps, 4) for nm in names}
         corners = ctx.stat(tag + "_corners")
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.cpu:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_lib as O
             threads = int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or (os.cpu_count() or 1)
@@ -1163,18 +1273,23 @@ def bench_config1(args, torch, dev, world, rank, local):
     ctx.reset_timing()
     elapsed = timed(torch, torch.distributed, dev, world, args.steps, step)
     live = {nm: round(ctx.kernel_time(nm)[0] / args.steps, 4) for nm in ("normals", "fpfh_spfh", "fpfh_weight")}
-    detail_steps = max(3, args.steps // 4)
-    ctx.set_timing(True)
-    ctx.reset_timing()
-    timed(torch, torch.distributed, dev, world, detail_steps, step)
-    if rank != 0:
-        ctx.close()
-        return
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"normals": torch.stack((b.nx, b.ny, b.nz, b.curv), 1).cpu().numpy(),
+                                         "descriptors": b.desc[:n].cpu().numpy()})
     names = ("normals", "fpfh_mark", "fpfh_spfh", "fpfh_weight", "grid_build", "normals_lists_small",
              "normals_lists_sparse", "normals_lists_dense", "normals_lists_wide", "normals_lists_query", "normals_chain",
              "normals_chain_big", "normals_long")
-    stages = {nm: round(ctx.kernel_time(nm)[0] / detail_steps, 4) for nm in names}
+    stages, detail_steps = None, 0
+    if args.full:  # the per-kernel breakdown: extra steps with every kernel timer on
+        detail_steps = max(3, args.steps // 4)
+        ctx.set_timing(True)
+        ctx.reset_timing()
+        timed(torch, torch.distributed, dev, world, detail_steps, step)
+        stages = {nm: round(ctx.kernel_time(nm)[0] / detail_steps, 4) for nm in names}
     ctx.set_timing(False)
+    if rank != 0:
+        ctx.close()
+        return
     pairs = ctx.stat("fpfh_spfh_pairs")
     nb = ctx.stat("normals_neighbors")
     spfh_ms, weight_ms = live["fpfh_spfh"], live["fpfh_weight"]
@@ -1191,7 +1306,7 @@ def bench_config1(args, torch, dev, world, rank, local):
     algo = kern[dom]["algorithmic_bytes_per_launch"]
     achieved = kern[dom]["achieved"] or 0.0
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.cpu:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
         threads = int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or (os.cpu_count() or 1)
@@ -1236,7 +1351,8 @@ def bench_config1(args, torch, dev, world, rank, local):
                      "algorithmic_bytes_per_launch": int(algo), "avg_ms": kern[dom]["ms"], "pairs_per_launch": int(pairs),
                      "note": kern[dom]["note"] + "; the dominant FPFH kernel of the step (live stage timers)",
                      "kernels": kern, "normals_neighbors": int(nb), "stages_ms_per_step": stages,
-                     "stages_basis": f"per-kernel HIP events over {detail_steps} extra steps after the timed region"},
+                     "stages_basis": (f"per-kernel HIP events over {detail_steps} extra steps after the timed region"
+                                      if args.full else "--full only")},
         "cpu_baseline": cpu,
     }
     print(json.dumps(line), flush=True)

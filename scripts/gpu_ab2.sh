@@ -5,6 +5,7 @@
 # two pairs each, alternating.  usage: bash scripts/gpu_ab2.sh [extra helper script]
 set -o pipefail
 mkdir -p gpurun_out
+T=$(mktemp -d)  # the bench line of each run (read back at once)
 BASE=$PWD/pcl_feature_extraction_amd/libpfx_base.so
 NEW=$PWD/pcl_feature_extraction_amd/libpfx.so
 for L in $BASE $NEW $BASE $NEW; do
@@ -15,7 +16,7 @@ done
 for i in 1 2; do
 for v in base new; do
   if [ $v = base ]; then L=$BASE; else L=$NEW; fi
-  PFX_LIB=$L timeout -k 10 300 python bench.py --no-cpu-baseline --no-e2e > gpurun_out/b_ab.json 2> gpurun_out/b_ab.err || { tail -20 gpurun_out/b_ab.err; exit 1; }
-  echo "$v $(python -c "import json; d=json.load(open('gpurun_out/b_ab.json')); r=d['roofline']; k=r['kernels_ms_per_scan']; print(d['value'], d['ms_per_step'], r['avg_ms'], json.dumps(k))")"
+  PFX_LIB=$L timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-e2e > $T/b_ab.json 2> $T/b_ab.err || { tail -20 $T/b_ab.err; exit 1; }
+  echo "$v $(python -c "import json; d=json.load(open('$T/b_ab.json')); r=d['roofline']; k=r['kernels_ms_per_scan']; print(d['value'], d['ms_per_step'], r['avg_ms'], json.dumps(k))")"
 done
 done

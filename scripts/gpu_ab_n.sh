@@ -5,6 +5,7 @@
 # repo root; a *_prof.so build prints its phase counters instead of taking part in the bench)
 set -o pipefail
 mkdir -p gpurun_out
+T=$(mktemp -d)  # the bench line of each run (read back at once)
 for r in 1 2; do
   for L in "$@"; do
     echo "== $(basename $L) normals_only"
@@ -15,7 +16,7 @@ done
 for r in 1 2; do
   for L in "$@"; do
     case $L in *_prof.so) continue;; esac
-    PFX_LIB=$PWD/$L timeout -k 10 300 python bench.py --no-cpu-baseline --no-e2e > gpurun_out/ab_n.json 2> gpurun_out/ab_n.err || { tail -30 gpurun_out/ab_n.err; exit 1; }
-    echo "bench $(basename $L) $(python -c "import json; d=json.load(open('gpurun_out/ab_n.json')); r=d['roofline']; c=r['chain']; k=r['kernels_ms_per_scan']; print(d['value'], d['ms_per_step'], 'stage', r['avg_ms'], 'chain', c['ms'], c['frac'], 'lists', round(k['normals_lists_small']+k['normals_lists_sparse']+k['normals_lists_dense']+k['normals_lists_query'],4), 'grid', k['grid_build'])")"
+    PFX_LIB=$PWD/$L timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-e2e > $T/ab_n.json 2> $T/ab_n.err || { tail -30 $T/ab_n.err; exit 1; }
+    echo "bench $(basename $L) $(python -c "import json; d=json.load(open('$T/ab_n.json')); r=d['roofline']; c=r['chain']; k=r['kernels_ms_per_scan']; print(d['value'], d['ms_per_step'], 'stage', r['avg_ms'], 'chain', c['ms'], c['frac'], 'lists', round(k['normals_lists_small']+k['normals_lists_sparse']+k['normals_lists_dense']+k['normals_lists_query'],4), 'grid', k['grid_build'])")"
   done
 done
