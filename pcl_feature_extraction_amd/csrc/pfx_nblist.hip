@@ -6,11 +6,15 @@
 // (wave-uniform cursors, no atomics), then orders each list with a wave-local LDS bucket sort on
 // d2 (exact (d2, caller index) rank inside a bucket).  The tile's lists are written to HBM
 // interleaved (stride 2^lg >= tile size) with one global atomic per tile.
-//   sparse tiles: <= 1280 candidates, <= 512 neighbours per query in LDS  (3 workgroups / CU)
-//   dense tiles:  <= 8000 candidates read from L2, <= 1024 neighbours per query (2 WG / CU)
-// Queries of larger blocks and overflowing lists go to k_nb_query (one 256-thread workgroup per
-// query, candidates streamed from L2/HBM, <= 4096 neighbours sorted in LDS); beyond that the
-// same kernel runs with its sort arrays in global scratch (<= 262144 neighbours).
+//   small tiles:  <= 384 candidates and neighbours per query in LDS
+//   sparse tiles: <= 1280 candidates, <= 512 neighbours per query in LDS
+//   dense tiles:  <= 8000 candidates read from L2, <= 1024 neighbours per query
+// (workgroups per CU, from the launch bounds -- 256 threads at 4 / 3 / 2 waves per SIMD -- and the
+// 160 KB of LDS per CU against 35.7 / 51.7 / 76.7 KB per workgroup: 4 / 3 / 2)
+// Tiles of larger blocks go to k_nb_wide, and their lists and the lists that overflow a tile to
+// k_nb_query: one workgroup per query (512 or 1024 threads), candidates streamed from L2/HBM,
+// <= 4096 / 8192 / 16384 neighbours sorted in LDS; beyond that the same kernel (256 threads) runs
+// with its sort arrays in global scratch (<= 262144 neighbours).
 #include <cstdlib>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
@@ -52,12 +56,51 @@ constexpr int kCapHuge = 1 << 18, kBucketsHuge = 4096, kHugeBlocks = PFX_HUGE_BL
 #define PFX_Q_WPE 6
 #endif
 constexpr int kNtQuery = PFX_NT_QUERY, kNtMid8 = PFX_NT_MID8, kNtMid = PFX_NT_MID, kNtHuge = 256;
-constexpr int kNCounters = 20;
+
+// The control block of a list build (device ints, zeroed by k_list_init, read back whole).
+// The tile counts come first: k_tile_class writes them once per build, so they survive a retry of
+// the list kernels (the set-up is not repeated); everything from kRetryFirst on is written by the
+// list kernels and zeroed again before each retry.
+enum Counter : int {
+  // tiles per class: written by k_tile_class, read by that class's kernel (its queue length)
+  // (the classifier queues the wide tiles' work entries too)
+  kTilesSmall, kTilesSparse, kTilesDense, kTilesWide,
+  // work per per-query tier (lists of <= 4k, 8k, 16k entries and beyond): appended by the tile,
+  // wide-tile and lower-tier kernels through TierQ, read by the tier's kernel
+  kWork4k, kRetryFirst = kWork4k, kWork8k, kWork16k, kWorkHuge,
+  // queue heads: the next item a workgroup of that kernel fetches (atomicAdd by the kernel)
+  kHeadSmall, kHeadSparse, kHeadDense, kHeadWide, kHead4k, kHead8k, kHead16k, kHeadHuge,
+  // the longest list no tier could hold (atomicMax by k_nb_query; > 0: PFX_ERR_CAPACITY)
+  kOverCap,
+  kNCounters
+};
+
+// The kernels a build may skip (wanted_tiers), as bits of the `_ran_mid_tiers` stat; the 4k and
+// huge tiers and the other tile kernels always run.  (The values are read by tests: frozen.)
+enum RanTier : int { kRan8k = 1, kRan16k = 2, kRanWide = 4, kRanAll = kRan8k | kRan16k | kRanWide };
+
+// Launch grids: persistent workgroups on dynamic queues, CUs x workgroups per CU x queue rounds.
+// Each launched workgroup may leave one unused arena tail in the list buffer, so the regrow bound
+// (kArenaTails) is built from these same names.
+constexpr int kCUs = 256;
+constexpr int kGridSmall = kCUs * 4 * 2;   // k_nb_tile, small: 4 resident per CU, twice over
+constexpr int kGridSparse = kCUs * 3 * 4;  // k_nb_tile, sparse: 3 resident per CU
+constexpr int kGridDense = kCUs * 2 * 4;   // k_nb_tile, dense: 2 resident per CU
+constexpr int kGridWide = kCUs * 4;        // k_nb_wide
+constexpr int kGrid4k = kCUs * 4;          // k_nb_query <= 4096 (3 resident per CU: the rest queue behind them)
+constexpr int kGrid8k = kCUs * 2;          // k_nb_query <= 8192
+constexpr int kGrid16k = kCUs;             // k_nb_query <= 16384
+constexpr int kGridHugeMax = kHugeBlocks;  // k_nb_query beyond: one workgroup per scratch slice, at most
+// the tile kernels reserve kArena entries at a time, the wide-tile and per-query kernels kArenaQuery
+constexpr size_t kArenaTails = (size_t)(kGridSmall + kGridSparse + kGridDense) * kArena +
+                               (size_t)(kGridWide + kGrid4k + kGrid8k + kGrid16k + kGridHugeMax) * kArenaQuery;
 
 // The lists of a wide tile are written unsorted to HBM by a test pass and ordered in place by the
 // per-query tiers: work items j | kListMode (the tier by k: <= 4096, <= 8192, <= 16384, beyond);
 // queue 0 also takes the test-mode items of the lists that overflow a tile kernel.
 constexpr int32_t kListMode = 1 << 30;
+// (the kernels get the queues through one pointer to a device copy, written by k_list_init: eight
+// pointers as kernel arguments pushed the tile kernels into spilling scalar registers)
 struct TierQ {
   int32_t* q[4];
   int* n[4];
@@ -144,17 +187,33 @@ __global__ void k_list_init(int32_t* __restrict__ qpos, int64_t n, const int32_t
   if (i == 0 && nq_src) *d_nq = (int64_t)*nq_src;
 }
 
-// deferred builds: the query count the consumers see is 0 unless the lists are whole (every
-// entry inside the list buffer, no query left for the first very-long-list pass, no capacity
-// overflow, a speculative grid that held every point): an invalid build is then never read
-// (its offsets may point past the buffer) and build_lists_check reruns the exact path
+// What a build's lists still lack, from its control block: 0 = the lists are whole.  The one
+// validity rule, shared by the device gate of a deferred build, its host check and the retry loop
+// of a synchronous build (which mends each lack in turn).  A list beyond every tier's capacity
+// (kOverCap) is not a lack but an error, handled by the callers.
+enum ListsLack : int {
+  // kRan8k | kRan16k | kRanWide: that kernel was skipped and had work
+  kLackGrid = 8,     // a speculative grid missed points (its out-of-bounds count)
+  kLackBuffer = 16,  // entries reserved past the list buffer's end
+  kLackScratch = 32  // lists for the huge tier and no scratch yet
+};
+__host__ __device__ inline int lists_lack(const int* counters, unsigned long long slots, unsigned long long cap,
+                                          bool have_huge, int ran, int oob) {
+  const int work = (counters[kWork8k] > 0 ? kRan8k : 0) | (counters[kWork16k] > 0 ? kRan16k : 0) |
+                   (counters[kTilesWide] > 0 ? kRanWide : 0);
+  return (work & ~ran) | (oob != 0 ? kLackGrid : 0) | (slots > cap ? kLackBuffer : 0) |
+         (!have_huge && counters[kWorkHuge] > 0 ? kLackScratch : 0);
+}
+
+// deferred builds: the query count the consumers see is 0 unless the lists are whole and no list
+// was over capacity: an invalid build is then never read (its offsets may point past the buffer)
+// and build_lists_check reruns the exact path
 __global__ void k_defer_gate(const int* __restrict__ counters, const unsigned long long* __restrict__ cursor,
-                             unsigned long long cap, int have_huge, int ran_mids, const int* __restrict__ oob,
+                             unsigned long long cap, int have_huge, int ran, const int* __restrict__ oob,
                              const int64_t* __restrict__ d_nq, int64_t* __restrict__ d_nq_eff) {
   if (threadIdx.x != 0) return;
-  const bool ok = cursor[0] <= cap && (have_huge || counters[3] == 0) && counters[4] == 0 && (!oob || *oob == 0) &&
-                  ((ran_mids & 1) || counters[14] == 0) && ((ran_mids & 2) || counters[12] == 0) &&
-                  ((ran_mids & 4) || counters[16] == 0);
+  const bool ok = lists_lack(counters, cursor[0], cap, have_huge != 0, ran, oob ? *oob : 0) == 0 &&
+                  counters[kOverCap] == 0;
   *d_nq_eff = ok ? *d_nq : 0;
 }
 
@@ -210,7 +269,7 @@ __global__ void __launch_bounds__(256) k_tile_class(GridView g, const int32_t* _
     const uint64_t m = __ballot(cls == c);
     if (!m) continue;
     int base = 0;
-    const int ci = c == 3 ? 10 : (c == 2 ? 16 : c);
+    const int ci = c == 3 ? kTilesSmall : (c == 2 ? kTilesWide : (c == 1 ? kTilesDense : kTilesSparse));
     if (lane == __builtin_ctzll(m)) base = atomicAdd(&counts[ci], __popcll(m));
     base = __shfl(base, __builtin_ctzll(m));
     if (cls == c) {
@@ -256,12 +315,13 @@ struct CandGlobal {
 // phase probes, accumulated in registers and added to the globals once per workgroup / wave at
 // the kernel's end (an atomic per probe left global atomics outstanding that the kernel's own
 // vmcnt waits then waited for, inflating the very phases they measured)
-__device__ unsigned long long g_tile_prof[28];
+constexpr int kTileProbes = 28, kWaveProbes = 12;
+__device__ unsigned long long g_tile_prof[kTileProbes];
 // per-wave probes (lane 0 of every wave): [class * 4 + i], class 0 small / 1 sparse / 2 dense;
 // i = 0 the wave's own sort work, 1 its wait at the barrier after the sort, 2 the staging round
 // (sort barrier -> staged registers stored), 3 the list-write loop
-__device__ unsigned long long g_tile_prof2[12];
-#define TPROF_DECL unsigned long long tacc_[28] = {}, wacc_[12] = {}
+__device__ unsigned long long g_tile_prof2[kWaveProbes];
+#define TPROF_DECL unsigned long long tacc_[kTileProbes] = {}, wacc_[kWaveProbes] = {}
 #define TPROF_T(v) long long v = (threadIdx.x == 0) ? clock64() : 0
 #define TPROF_ADD(i, a, b) tacc_[i] += (unsigned long long)((b) - (a))
 #define WPROF_T(v) long long v = ((threadIdx.x & 63) == 0) ? clock64() : 0
@@ -269,10 +329,10 @@ __device__ unsigned long long g_tile_prof2[12];
 #define TPROF_FLUSH                                                                      \
   do {                                                                                   \
     if (threadIdx.x == 0)                                                                \
-      _Pragma("unroll") for (int i_ = 0; i_ < 28; ++i_)                                  \
+      _Pragma("unroll") for (int i_ = 0; i_ < kTileProbes; ++i_)                         \
         if (tacc_[i_]) atomicAdd(&g_tile_prof[i_], tacc_[i_]);                           \
     if ((threadIdx.x & 63) == 0)                                                         \
-      _Pragma("unroll") for (int i_ = 0; i_ < 12; ++i_)                                  \
+      _Pragma("unroll") for (int i_ = 0; i_ < kWaveProbes; ++i_)                         \
         if (wacc_[i_]) atomicAdd(&g_tile_prof2[i_], wacc_[i_]);                          \
   } while (0)
 #else
@@ -515,8 +575,6 @@ __device__ __forceinline__ void sort_list(uint16_t* L, int k, float qx, float qy
 // so the one global-latency round of a tile (staging loads, list stores) is shared.  Tiles come
 // from a dynamic queue `chunk` at a time; thread 0 keeps the next chunk's base fetched one chunk
 // ahead and publishes it in [D].
-// (the kernels get the queues through one pointer to a device copy: eight pointers as kernel
-// arguments pushed the tile kernels into spilling scalar registers)
 __device__ __forceinline__ void push_sort(const TierQ* tq, int32_t j, int k) {
   const int t = query_tier(k);
   tq->q[t][atomicAdd(tq->n[t], 1)] = j | kListMode;
@@ -1102,9 +1160,11 @@ __device__ __forceinline__ void bucket_scan(const int* bcount, int* bpos, int* w
 // (16 KB: with its one bucket array, 16 KB, the tier keeps four workgroups per CU)
 constexpr int kRankWindow = 4096;
 
-// NT (round 6): 512 threads for the 4k tier, 1024 for the 8k and 16k tiers -- their LDS, not their
-// registers, caps the workgroups per CU (4 / 2 / 1), so a wider workgroup shortens each list's
-// chain of dependent latency rounds at the same LDS (the 16k tier ran one wave per SIMD).
+// NT (round 6): 512 threads for the 4k tier, 1024 for the 8k and 16k tiers -- their LDS (40.1 / 72.1
+// / 144.1 KB per workgroup, of 160 KB per CU) caps the workgroups per CU at 3 / 2 / 1, and the
+// launch bounds hold the registers to the same (WPE = 6 / 8 / 4 waves per SIMD = 3 / 2 / 1
+// workgroups of 8 / 16 / 16 waves), so a wider workgroup shortens each list's chain of dependent
+// latency rounds at the same LDS (the 16k tier ran one wave per SIMD).
 // GLOBAL (the > 16k tier): one bucket array (counts, scanned in place to starts, advanced by the
 // scatter to ends: a bucket is [end of b - 1, end of b)), eight entries per thread in flight in
 // the passes over the scratch, the rank pass through LDS windows
@@ -1487,131 +1547,202 @@ std::string bname(const char* tag, const char* what) { return std::string(tag) +
 struct ListsRb {
   int cnt[kNCounters];
   int oob;
-  int pad;
   unsigned long long cur[4];
   int64_t nq;
 };
 
-}  // namespace
+// one synchronisation per readback: counters, cursors, the query count (and a speculative grid's
+// out-of-bounds count) in one pinned block
+const ListsRb* read_back(pfx_ctx* ctx, const void* counters, const void* cursor, const void* d_nq, const int* oob) {
+  hipStream_t st = ctx->stream;
+  ListsRb* rb = ctx->readback<ListsRb>();
+  PFX_HIP(hipMemcpyAsync(rb->cnt, counters, sizeof(rb->cnt), hipMemcpyDeviceToHost, st));
+  PFX_HIP(hipMemcpyAsync(rb->cur, cursor, sizeof(rb->cur), hipMemcpyDeviceToHost, st));
+  PFX_HIP(hipMemcpyAsync(&rb->nq, d_nq, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  rb->oob = 0;
+  if (oob) PFX_HIP(hipMemcpyAsync(&rb->oob, oob, sizeof(int), hipMemcpyDeviceToHost, st));
+  ctx->sync_spin(st);
+  return rb;
+}
+
+[[noreturn]] void throw_over_cap(const char* tag, int k) {
+  throw Error(PFX_ERR_CAPACITY, std::string(tag) + ": a query has " + std::to_string(k) + " neighbours (> " +
+                                    std::to_string(kCapHuge) + " supported)");
+}
+
+// The host's half of `out` and the build's stats, from the readback block of whole lists: the one
+// publisher, of synchronous builds and of checked deferred ones
+void publish(pfx_ctx* ctx, const char* tag, const ListsRb& rb, size_t list_words, NbLists& out) {
+  out.nq = rb.nq;
+  out.nq_dev = nullptr;
+  out.total = (int64_t)rb.cur[1];
+  out.long_total = (int64_t)rb.cur[2];
+  out.long_nq = (int64_t)rb.cur[3];
+  out.slots = (int64_t)rb.cur[0];
+  auto stat = [&](const char* what) -> int64_t& { return ctx->stats[std::string(tag) + what]; };
+  stat("_tiles_sparse") = rb.cnt[kTilesSparse];
+  stat("_tiles_dense") = rb.cnt[kTilesDense];
+  stat("_wide") = rb.cnt[kTilesWide];
+  stat("_single") = rb.cnt[kWork4k];
+  stat("_mid8") = rb.cnt[kWork8k];
+  stat("_mid") = rb.cnt[kWork16k];
+  stat("_huge") = rb.cnt[kWorkHuge];
+  stat("_slots") = (int64_t)rb.cur[0];  // list words reserved (entries + padding + arena tails)
+  stat("_list_words") = (int64_t)list_words;
+}
 
 // The 4k-8k and 8k-16k per-query tiers need 72 / 144 KB of LDS per workgroup, so even an empty
 // launch waits until whole CUs are free of the concurrent NARF stream's workgroups (150-200 us on
-// the headline's critical path, whose lists never reach these tiers).  A tier is launched while
-// one of the last 16 builds of this (context, tag) had work for it (always on the first build);
-// a skipped tier that turns out to have work is launched after the readback (or, for a deferred
-// build, the lists are rebuilt exactly), so results never depend on the hint.
-static bool mid_tier_wanted(pfx_ctx* ctx, const char* tag, const char* which) {
-  const auto it = ctx->stats.find(std::string(tag) + which);
-  return it == ctx->stats.end() || it->second > 0;
+// the headline's critical path, whose lists never reach these tiers); an empty launch of the
+// wide-tile kernel waits for whole CUs beside NARF in the same way.  Such a kernel is launched
+// while one of the last 16 builds of this (context, tag) had work for it (always on the first
+// build); a skipped one that turns out to have work is launched after the readback (or, for a
+// deferred build, the lists are rebuilt exactly), so results never depend on the hint.
+struct TierHint {
+  const char* key;
+  RanTier bit;
+  Counter work;
+};
+constexpr TierHint kTierHints[3] = {
+    {"_hint_mid8", kRan8k, kWork8k}, {"_hint_mid", kRan16k, kWork16k}, {"_hint_wide", kRanWide, kTilesWide}};
+int wanted_tiers(pfx_ctx* ctx, const char* tag) {
+  int ran = 0;
+  for (const TierHint& h : kTierHints) {
+    const auto it = ctx->stats.find(std::string(tag) + h.key);
+    if (it == ctx->stats.end() || it->second > 0) ran |= h.bit;
+  }
+  return ran;
 }
-static void note_mid_tiers(pfx_ctx* ctx, const char* tag, const int* h_cnt) {
-  static const char* const keys[3] = {"_hint_mid8", "_hint_mid", "_hint_wide"};
-  for (int t = 0; t < 3; ++t) {
-    const std::string key = std::string(tag) + keys[t];
-    const int work = h_cnt[t == 0 ? 14 : (t == 1 ? 12 : 16)];
-    int64_t& v = ctx->stats[key];
-    v = work > 0 ? 16 : std::max<int64_t>(0, v - 1);
+void note_mid_tiers(pfx_ctx* ctx, const char* tag, const int* h_cnt) {
+  for (const TierHint& h : kTierHints) {
+    int64_t& v = ctx->stats[std::string(tag) + h.key];
+    v = h_cnt[h.work] > 0 ? 16 : std::max<int64_t>(0, v - 1);
   }
 }
 
-bool build_lists_check(pfx_ctx* ctx, const Grid& G, NbLists& out, const char* tag) {
-  hipStream_t st = ctx->stream;
-  auto B = [&](const char* what) -> DevBuf& { return ctx->bufs[bname(tag, what)]; };
-  ListsRb* rb = ctx->readback<ListsRb>();
-  PFX_HIP(hipMemcpyAsync(rb->cnt, B("counters").ptr, sizeof(rb->cnt), hipMemcpyDeviceToHost, st));
-  PFX_HIP(hipMemcpyAsync(rb->cur, B("cursor").ptr, sizeof(rb->cur), hipMemcpyDeviceToHost, st));
-  PFX_HIP(hipMemcpyAsync(&rb->nq, B("nq").ptr, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  rb->oob = 0;
-  if (G.oob) PFX_HIP(hipMemcpyAsync(&rb->oob, G.oob, sizeof(int), hipMemcpyDeviceToHost, st));
-  ctx->sync_spin(st);
-  const int* h_cnt = rb->cnt;
-  const unsigned long long* h_cur = rb->cur;
-  const DevBuf& lb = B("list");
-  if (rb->oob > 0) return false;                                    // speculative grid too small
-  if (h_cur[0] > lb.bytes / sizeof(uint32_t)) return false;         // list buffer too small
-  if (!B("scratch").ptr && h_cnt[3] > 0) return false;              // first very long lists
-  const int ran = (int)ctx->stats[std::string(tag) + "_ran_mid_tiers"];
-  note_mid_tiers(ctx, tag, h_cnt);
-  if ((!(ran & 1) && h_cnt[14] > 0) || (!(ran & 2) && h_cnt[12] > 0) || (!(ran & 4) && h_cnt[16] > 0))
-    return false;  // a skipped tier had work
-  if (h_cnt[4] > 0)
-    throw Error(PFX_ERR_CAPACITY, std::string(tag) + ": a query has " + std::to_string(h_cnt[4]) +
-                                      " neighbours (> " + std::to_string(kCapHuge) + " supported)");
-  out.nq = rb->nq;
-  out.nq_dev = nullptr;
-  out.total = (int64_t)h_cur[1];
-  out.long_total = (int64_t)h_cur[2];
-  out.long_nq = (int64_t)h_cur[3];
-  out.slots = (int64_t)h_cur[0];
-  ctx->stats[std::string(tag) + "_tiles_sparse"] = h_cnt[0];
-  ctx->stats[std::string(tag) + "_tiles_dense"] = h_cnt[1];
-  ctx->stats[std::string(tag) + "_single"] = h_cnt[2];
-  ctx->stats[std::string(tag) + "_huge"] = h_cnt[3];
-  ctx->stats[std::string(tag) + "_mid"] = h_cnt[12];
-  ctx->stats[std::string(tag) + "_wide"] = h_cnt[16];
-  ctx->stats[std::string(tag) + "_slots"] = (int64_t)h_cur[0];
-  ctx->stats[std::string(tag) + "_list_words"] = (int64_t)(lb.bytes / sizeof(uint32_t));
-  return true;
+#ifdef PFX_SHOT_PROFILE
+void report_probes(const char* tag) {
+  unsigned long long pr[kTileProbes];
+  PFX_HIP(hipMemcpyFromSymbol(pr, HIP_SYMBOL(g_tile_prof), sizeof(pr)));
+  fprintf(stderr, "%s wave_sort cycles (wave 0): count %llu scan %llu scatter %llu rank %llu\n", tag, pr[8],
+          pr[9], pr[10], pr[11]);
+  fprintf(stderr, "%s tile cycles: sparse stage %llu test %llu sort %llu write %llu | dense - %llu test %llu "
+          "sort %llu write %llu | small - %llu test %llu sort %llu write %llu (cumulative)\n", tag, pr[0], pr[1], pr[2],
+          pr[3], pr[4], pr[5], pr[6], pr[7], pr[16], pr[17], pr[18], pr[19]);
+  fprintf(stderr, "%s query cycles: test %llu sort+write %llu | entries %llu candidates %llu\n", tag, pr[20],
+          pr[21], pr[22], pr[23]);
+  fprintf(stderr, "%s query 4k-tier phases: scan %llu scatter %llu rank+write %llu | list-mode items %llu\n", tag,
+          pr[24], pr[25], pr[26], pr[27]);
+  unsigned long long pw[kWaveProbes];
+  PFX_HIP(hipMemcpyFromSymbol(pw, HIP_SYMBOL(g_tile_prof2), sizeof(pw)));
+  fprintf(stderr, "%s wave cycles (sum over waves): small sort %llu sortwait %llu staging %llu listwrite %llu | "
+          "sparse %llu %llu %llu %llu | dense %llu %llu %llu %llu\n", tag, pw[0], pw[1], pw[2], pw[3], pw[4], pw[5],
+          pw[6], pw[7], pw[8], pw[9], pw[10], pw[11]);
+  static const unsigned long long zw[kWaveProbes] = {};
+  PFX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_tile_prof2), zw, sizeof(zw)));
+  static const unsigned long long zero[kTileProbes] = {};
+  PFX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_tile_prof), zero, sizeof(zero)));
 }
+#endif
 
-void build_lists(pfx_ctx* ctx, const Grid& G, const uint8_t* mask, double radius, bool sorted, NbLists& out,
-                 const char* tag, bool defer, int want, bool compact, bool gate) {
-  hipStream_t st = ctx->stream;
-  const int64_t n = G.n;
-  GridView g = view(G);
-  const float rr = (float)(radius * radius);
-  out = NbLists();
-  if (n == 0) return;
-  if (n >= (int64_t(1) << 28))
-    throw Error(PFX_ERR_CAPACITY, std::string(tag) + ": neighbour lists support < 2^28 points");
-  auto B = [&](const char* what) -> DevBuf& { return ctx->bufs[bname(tag, what)]; };
-  int32_t* qpos = B("qpos").as<int32_t>(n);
-  int64_t* d_nq = B("nq").as<int64_t>(1);
-  uint8_t* flags = B("flags").as<uint8_t>(n);
-  int32_t* seg = B("seg").as<int32_t>(n);
-  int32_t* tiles = B("tiles").as<int32_t>(n);
-  int64_t* d_ntiles = B("ntiles").as<int64_t>(1);
-  // tile records: small at [0, n), sparse at [n, 2n) upward, dense at [n, 2n) downward
-  int32_t* recs = B("recs").as<int32_t>((size_t)2 * n * kRecInts);
-  int32_t* single = B("single").as<int32_t>(n);
-  int32_t* huge = B("huge").as<int32_t>(n);
-  int64_t* off = B("off").as<int64_t>(n);
-  int32_t* cnt = B("cnt").as<int32_t>(n);
-  uint8_t* lgs = B("lg").as<uint8_t>(n);
-  // counters: 0 sparse tiles, 1 dense tiles, 2 per-query work, 3 huge work, 4 max k over cap,
-  // 5 / 7 sparse / dense tile queue heads, 6 unused, 8 / 9 per-query / huge work queue heads,
-  // 10 small tiles, 11 their queue head,
-  // 12 mid work (lists of 8k-16k entries), 13 its queue head, 14 mid8 work (4k-8k), 15 its head,
-  // 16 wide-tile work (queued by the classifier), 17 its queue head
-  int* counters = B("counters").as<int>(kNCounters);
-  int32_t* wq = B("wide").as<int32_t>((size_t)n);  // wide-tile work: record indices
-  int32_t* mid = B("mid").as<int32_t>(n);
-  int32_t* mid8 = B("mid8").as<int32_t>(n);
-  int32_t* qrec = B("qrec").as<int32_t>((size_t)n * kRecInts);
-  unsigned long long* cursor = B("cursor").as<unsigned long long>(4);
-  size_t t1 = 0, t2 = 0, t3 = 0;
-  PFX_HIP(rocprim::select(nullptr, t1, rocprim::counting_iterator<int32_t>(0), flags, qpos, d_nq, (size_t)n, st));
-  PFX_HIP(rocprim::inclusive_scan(nullptr, t2, seg, seg, (size_t)n, rocprim::maximum<int32_t>(), st));
-  PFX_HIP(rocprim::select(nullptr, t3, rocprim::counting_iterator<int32_t>(0), flags, tiles, d_ntiles, (size_t)n,
-                          st));
-  void* tmp = B("tmp").get(std::max(t1, std::max(t2, t3)) + 16);
-  const unsigned nb = (unsigned)ceil_div(n, 256);
-  unsigned long long* cursor0 = B("cursor").as<unsigned long long>(4);
-  // sort-only work (kListMode) of the lists the tile kernels write unsorted, by length; the
-  // kernels read the queues from a device copy written by k_list_init
-  constexpr bool use_mid8 = true;  // the 4k-8k tier (round 3; without it those lists take the 16k tier)
-  const TierQ tq{{single, use_mid8 ? mid8 : mid, mid, huge},
-                 {counters + 2, counters + (use_mid8 ? 14 : 12), counters + 12, counters + 3}};
-  TierQ* tq_dev = static_cast<TierQ*>(B("tierq").get(sizeof(TierQ)));
-  {
+// One list build: its buffers (the context's named scratch, by tag) and the steps build_lists
+// takes with them.
+struct ListBuild {
+  pfx_ctx* ctx;
+  const Grid& G;
+  const char* tag;
+  hipStream_t st;
+  const int64_t n;
+  const GridView g;
+  const float rr;
+  const int isort, compact;
+  int32_t *qpos, *seg, *tiles, *recs, *wq, *qrec, *cnt;
+  int32_t *q4k, *q8k, *q16k, *qhuge;  // the per-query tiers' work queues (TierQ order)
+  int64_t *d_nq, *d_ntiles, *off;
+  uint8_t *flags, *lgs;
+  int* counters;               // [kNCounters], see Counter
+  unsigned long long* cursor;  // [4], see ListOut
+  TierQ* tq_dev;
+  size_t t1 = 0, t2 = 0, t3 = 0;  // rocprim workspace of the set-up's two selects and its scan
+  void* tmp;
+  DevBuf &lb, &hs;  // the list buffer; the huge tier's scratch (absent until a build needs it)
+  int ch_small, ch_sparse, ch_dense;
+  // one 4 MB scratch slice per workgroup of the persistent huge tier: as many workgroups as
+  // slices (sized from the queue length the first time it was seen, 256 to kHugeBlocks: a
+  // context holds 1-4 GB only when that many lists above 16k entries exist)
+  static constexpr size_t kHugeSlice = sizeof(uint32_t) * 4 * (size_t)kCapHuge;
+
+  DevBuf& buf(const char* what) { return ctx->bufs[bname(tag, what)]; }
+
+  // step 1: the buffers
+  ListBuild(pfx_ctx* c, const Grid& grid, const char* t, double radius, bool sorted, bool compact_)
+      : ctx(c), G(grid), tag(t), st(c->stream), n(grid.n), g(view(grid)), rr((float)(radius * radius)),
+        isort(sorted ? 1 : 0), compact(compact_ ? 1 : 0), lb(buf("list")), hs(buf("scratch")) {
+    qpos = buf("qpos").as<int32_t>(n);
+    d_nq = buf("nq").as<int64_t>(1);
+    flags = buf("flags").as<uint8_t>(n);
+    seg = buf("seg").as<int32_t>(n);
+    tiles = buf("tiles").as<int32_t>(n);
+    d_ntiles = buf("ntiles").as<int64_t>(1);
+    // tile records: small at [0, n), sparse at [n, 2n) upward, dense at [n, 2n) downward
+    recs = buf("recs").as<int32_t>((size_t)2 * n * kRecInts);
+    q4k = buf("single").as<int32_t>(n);
+    qhuge = buf("huge").as<int32_t>(n);
+    off = buf("off").as<int64_t>(n);
+    cnt = buf("cnt").as<int32_t>(n);
+    lgs = buf("lg").as<uint8_t>(n);
+    counters = buf("counters").as<int>(kNCounters);
+    wq = buf("wide").as<int32_t>((size_t)n);  // wide-tile work: record indices
+    q16k = buf("mid").as<int32_t>(n);
+    q8k = buf("mid8").as<int32_t>(n);
+    qrec = buf("qrec").as<int32_t>((size_t)n * kRecInts);
+    cursor = buf("cursor").as<unsigned long long>(4);
+    PFX_HIP(rocprim::select(nullptr, t1, rocprim::counting_iterator<int32_t>(0), flags, qpos, d_nq, (size_t)n, st));
+    PFX_HIP(rocprim::inclusive_scan(nullptr, t2, seg, seg, (size_t)n, rocprim::maximum<int32_t>(), st));
+    PFX_HIP(rocprim::select(nullptr, t3, rocprim::counting_iterator<int32_t>(0), flags, tiles, d_ntiles, (size_t)n,
+                            st));
+    tmp = buf("tmp").get(std::max(t1, std::max(t2, t3)) + 16);
+    tq_dev = static_cast<TierQ*>(buf("tierq").get(sizeof(TierQ)));
+    if (!lb.ptr) {
+      // (PFX_LIST_WORDS: the first buffer's size in 32-bit words, for tests of the capacity guards
+      // and the regrow path; the buffer grows as needed either way)
+      size_t words = 64 * (size_t)(n + 1);
+      if (const char* e = std::getenv("PFX_LIST_WORDS")) words = std::max<size_t>(256, std::strtoull(e, nullptr, 10));
+      lb.get(sizeof(uint32_t) * words);
+    }
+    // tiles per queue fetch, per class: many cheap small tiles amortise the queue atomic over 4,
+    // the heavy sparse / dense tiles balance better with 2 / 1 at ~1M queries (sweep S/P/D on the
+    // 1M-pt room, configs[1] and Harris3D: 4/4/4 162.7, 31.7, 230.4; 4/2/2 166.0, 33.2, 230.3;
+    // 4/2/1 166.6, 34.9, 229.6; 2/2/2 166.5, 33.5, 208.4 Mpoints/s), while the 10M-pt dense
+    // variant, with ~10x the heavy tiles per workgroup, wants 4 again (P/D 2/1 8.83, 2/2 9.11,
+    // 2/4 9.22, 4/4 9.25 Mpoints/s): the heavy classes take n / 2M tiles per fetch, clamped to
+    // [2, 4] / [1, 4]
+    const int heavy = (int)std::min<int64_t>(4, n >> 21);
+    ch_small = 4;
+    ch_sparse = std::max(2, heavy);
+    ch_dense = std::max(1, heavy);
+  }
+
+  size_t list_words() const { return lb.bytes / sizeof(uint32_t); }
+  ListOut list_out() const {
+    return ListOut{off, cnt, lgs, static_cast<uint32_t*>(lb.ptr), cursor, list_words(), compact, qrec};
+  }
+
+  // step 2: control block zeroed, query positions (masked or all), cell segments, tiles and
+  // their classification -- once per build, whatever the list kernels need afterwards
+  void setup(const uint8_t* mask, int want) {
+    const unsigned nb = (unsigned)ceil_div(n, 256);
+    // sort-only work (kListMode) of the lists the tile kernels write unsorted, by length
+    const TierQ tq{{q4k, q8k, q16k, qhuge},
+                   {counters + kWork4k, counters + kWork8k, counters + kWork16k, counters + kWorkHuge}};
     TimeScope ts(ctx, std::string(tag) + "_tiles");
     if (mask) {
-      k_list_init<<<1, 256, 0, st>>>(nullptr, 0, nullptr, d_nq, counters, kNCounters, cursor0, tq, tq_dev);
+      k_list_init<<<1, 256, 0, st>>>(nullptr, 0, nullptr, d_nq, counters, kNCounters, cursor, tq, tq_dev);
       k_mask_flags<<<nb, 256, 0, st>>>(G.perm, G.skeys, n, (uint64_t)G.ncells, mask, want, flags);
       PFX_HIP(rocprim::select(tmp, t1, rocprim::counting_iterator<int32_t>(0), flags, qpos, d_nq, (size_t)n, st));
     } else {
       // every finite point, in cell order: sorted positions [0, cell_start[ncells])
-      k_list_init<<<nb, 256, 0, st>>>(qpos, n, G.cell_start + G.ncells, d_nq, counters, kNCounters, cursor0, tq,
+      k_list_init<<<nb, 256, 0, st>>>(qpos, n, G.cell_start + G.ncells, d_nq, counters, kNCounters, cursor, tq,
                                       tq_dev);
     }
     k_seg_marks<<<nb, 256, 0, st>>>(qpos, G.skeys, d_nq, seg);
@@ -1621,241 +1752,228 @@ void build_lists(pfx_ctx* ctx, const Grid& G, const uint8_t* mask, double radius
     k_tile_class<<<nb, 256, 0, st>>>(g, qpos, G.skeys, d_nq, tiles, d_ntiles, recs, n, wq, counters);
     check_launch("nblist tiles");
   }
-  const size_t lds_q = sizeof(uint32_t) * 2 * kCapQuery;
-  PFX_HIP(hipFuncSetAttribute((const void*)k_nb_query<kCapQuery, kBucketsQuery, false, kNtQuery, PFX_Q_WPE>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
-  const size_t lds_m8 = sizeof(uint32_t) * 2 * kCapMid8;
-  PFX_HIP(hipFuncSetAttribute((const void*)k_nb_query<kCapMid8, kBucketsMid8, false, kNtMid8, kNtMid8 / 128>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m8));
-  const size_t lds_m = sizeof(uint32_t) * 2 * kCapMid;
-  PFX_HIP(hipFuncSetAttribute((const void*)k_nb_query<kCapMid, kBucketsMid, false, kNtMid, kNtMid / 256>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
-  DevBuf& lb = B("list");
-  if (!lb.ptr) {
-    // (PFX_LIST_WORDS: the first buffer's size in 32-bit words, for tests of the capacity guards
-    // and the regrow path; the buffer grows as needed either way)
-    size_t words = 64 * (size_t)(n + 1);
-    if (const char* e = std::getenv("PFX_LIST_WORDS")) words = std::max<size_t>(256, std::strtoull(e, nullptr, 10));
-    lb.get(sizeof(uint32_t) * words);
+
+  // before a retry: everything the list kernels wrote is zeroed (the first attempt's was by
+  // k_list_init); the tile counts below kRetryFirst are the classifier's and stay
+  void reset_for_retry() {
+    PFX_HIP(hipMemsetAsync(cursor, 0, 4 * sizeof(unsigned long long), st));
+    PFX_HIP(hipMemsetAsync(counters + kRetryFirst, 0, (kNCounters - kRetryFirst) * sizeof(int), st));
   }
-  const int isort = sorted ? 1 : 0;
-  // tiles per queue fetch, per class: many cheap small tiles amortise the queue atomic over 4,
-  // the heavy sparse / dense tiles balance better with 2 / 1 at ~1M queries (sweep S/P/D on the
-  // 1M-pt room, configs[1] and Harris3D: 4/4/4 162.7, 31.7, 230.4; 4/2/2 166.0, 33.2, 230.3;
-  // 4/2/1 166.6, 34.9, 229.6; 2/2/2 166.5, 33.5, 208.4 Mpoints/s), while the 10M-pt dense
-  // variant, with ~10x the heavy tiles per workgroup, wants 4 again (P/D 2/1 8.83, 2/2 9.11,
-  // 2/4 9.22, 4/4 9.25 Mpoints/s): the heavy classes take n / 2M tiles per fetch, clamped to
-  // [2, 4] / [1, 4]
-  const int heavy = (int)std::min<int64_t>(4, n >> 21);
-  const int ch_small = 4, ch_sparse = std::max(2, heavy), ch_dense = std::max(1, heavy);
-  for (int attempt = 0; attempt < 3; ++attempt) {
-    ListOut lo{off, cnt, lgs, static_cast<uint32_t*>(lb.ptr), cursor, lb.bytes / sizeof(uint32_t), compact ? 1 : 0, qrec};
-    if (attempt) {  // (the first attempt's cursors were zeroed by k_list_init)
-      PFX_HIP(hipMemsetAsync(cursor, 0, 4 * sizeof(unsigned long long), st));
-      PFX_HIP(hipMemsetAsync(counters + 2, 0, sizeof(int), st));  // per-query work
-      PFX_HIP(hipMemsetAsync(counters + 3, 0, 3 * sizeof(int), st));  // huge, max k, sparse queue
-      PFX_HIP(hipMemsetAsync(counters + 7, 0, 3 * sizeof(int), st));  // dense, query, huge queues
-      PFX_HIP(hipMemsetAsync(counters + 11, 0, 5 * sizeof(int), st));  // small queue, mid / mid8 work + queues
-      PFX_HIP(hipMemsetAsync(counters + 17, 0, sizeof(int), st));  // wide queue (its work: the classifier's)
-    }
-    // one synchronisation per call: counters, cursors and the query count in one pinned block
-    ListsRb* rb = ctx->readback<ListsRb>();
-    auto read_back = [&] {
-      PFX_HIP(hipMemcpyAsync(rb->cnt, counters, sizeof(rb->cnt), hipMemcpyDeviceToHost, st));
-      PFX_HIP(hipMemcpyAsync(rb->cur, cursor, sizeof(rb->cur), hipMemcpyDeviceToHost, st));
-      PFX_HIP(hipMemcpyAsync(&rb->nq, d_nq, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-      ctx->sync_spin(st);
-    };
-    DevBuf& hs = B("scratch");
-    auto launch_mid8 = [&] {
-      k_nb_query<kCapMid8, kBucketsMid8, false, kNtMid8, kNtMid8 / 128><<<256 * 2, kNtMid8, lds_m8, st>>>(
-          g, mid8, counters + 14, rr, (float)kBucketsMid8 / rr, isort, lo, tq_dev, counters + 4, nullptr,
-          counters + 15);
-      check_launch("nblist 8k lists");
-    };
-    auto launch_mid = [&] {
-      k_nb_query<kCapMid, kBucketsMid, false, kNtMid, kNtMid / 256><<<256, kNtMid, lds_m, st>>>(
-          g, mid, counters + 12, rr, (float)kBucketsMid / rr, isort, lo, tq_dev, counters + 4, nullptr,
-          counters + 13);
-      check_launch("nblist 16k lists");
-    };
-    // (see mid_tier_wanted; a rerun launches every tier)
-    // (bit 4: the wide-tile kernel -- an empty launch of it also waits for whole CUs beside NARF)
-    const int ran_mids = attempt ? 7 : ((use_mid8 && mid_tier_wanted(ctx, tag, "_hint_mid8") ? 1 : 0) |
-                                        (mid_tier_wanted(ctx, tag, "_hint_mid") ? 2 : 0) | (use_mid8 ? 0 : 1) |
-                                        (mid_tier_wanted(ctx, tag, "_hint_wide") ? 4 : 0));
-    ctx->stats[std::string(tag) + "_ran_mid_tiers"] = ran_mids;
-    // one 4 MB scratch slice per workgroup of the persistent huge tier: as many workgroups as
-    // slices (sized from the queue length the first time it was seen, 256 to kHugeBlocks: a
-    // context holds 1-4 GB only when that many lists above 16k entries exist)
-    const size_t huge_slice = sizeof(uint32_t) * 4 * (size_t)kCapHuge;
-    auto huge_blocks = [&] { return (unsigned)std::min<size_t>(kHugeBlocks, hs.bytes / huge_slice); };
-    auto huge_alloc = [&](int count) {
-      hs.get(huge_slice * (size_t)std::min(kHugeBlocks, std::max(256, count)));
-    };
-    auto launch_huge = [&] {
-      k_nb_query<kCapHuge, kBucketsHuge, true, kNtHuge, 4><<<huge_blocks(), kNtHuge, 0, st>>>(
-          g, huge, counters + 3, rr, (float)kBucketsHuge / rr, isort, lo, nullptr, counters + 4,
-          static_cast<uint32_t*>(hs.ptr), counters + 9);
-      check_launch("nblist huge lists");
-    };
-    if (gate && ctx->lists_gate) {  // pfx_normals_gate_dev: the caller's event, once, right before the list kernels
-      // (after the list set-up above, which therefore overlaps the gated stage)
-      PFX_HIP(hipStreamWaitEvent(st, ctx->lists_gate, 0));
-      ctx->lists_gate = nullptr;
+
+  // one per-query tier (the template arguments as compiled for it): its grid, queue, work count
+  // and queue head; the LDS tiers sort in 2 * CAP words of dynamic LDS and pass longer lists on
+  // through the queues, the GLOBAL tier sorts in `scratch` and has no tier above it
+  template <int CAP, int NB, bool GLOBAL, int NT, int WPE>
+  void launch_tier(unsigned grid, const int32_t* work, Counter count, Counter head, uint32_t* scratch,
+                   const char* what) {
+    const auto kern = k_nb_query<CAP, NB, GLOBAL, NT, WPE>;
+    const size_t lds = GLOBAL ? 0 : sizeof(uint32_t) * 2 * CAP;
+    if (lds) PFX_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kern<<<grid, NT, lds, st>>>(g, work, counters + count, rr, (float)NB / rr, isort, list_out(),
+                                GLOBAL ? nullptr : tq_dev, counters + kOverCap, scratch, counters + head);
+    check_launch(what);
+  }
+  void launch_4k() {
+    launch_tier<kCapQuery, kBucketsQuery, false, kNtQuery, PFX_Q_WPE>(kGrid4k, q4k, kWork4k, kHead4k, nullptr,
+                                                                      "nblist 4k lists");
+  }
+  // lists of 4k-8k entries (dense clouds: ~14 % of the 10M-pt room's queries, 31 % of its
+  // entries) in two 72 KB workgroups per CU instead of the 16k tier's one (10M-pt dense
+  // variant: per-query lists 750 -> 650 ms, 1066 -> 968 ms per step); the count stays on the device
+  void launch_8k() {
+    launch_tier<kCapMid8, kBucketsMid8, false, kNtMid8, kNtMid8 / 128>(kGrid8k, q8k, kWork8k, kHead8k, nullptr,
+                                                                        "nblist 8k lists");
+  }
+  // lists of up to 16k entries, one 144 KB workgroup per CU
+  void launch_16k() {
+    launch_tier<kCapMid, kBucketsMid, false, kNtMid, kNtMid / 256>(kGrid16k, q16k, kWork16k, kHead16k, nullptr,
+                                                                    "nblist 16k lists");
+  }
+  unsigned huge_blocks() const { return (unsigned)std::min<size_t>(kGridHugeMax, hs.bytes / kHugeSlice); }
+  void launch_huge() {
+    launch_tier<kCapHuge, kBucketsHuge, true, kNtHuge, 4>(huge_blocks(), qhuge, kWorkHuge, kHeadHuge,
+                                                          static_cast<uint32_t*>(hs.ptr), "nblist huge lists");
+  }
+
+  // step 3: one attempt's list kernels; `ran`: the skippable ones to launch (RanTier)
+  void launch_lists(int ran) {
+    const ListOut lo = list_out();
+    const float bscale = 256.0f / rr;
+    TimeScope ts(ctx, std::string(tag) + "_lists");
+    {
+      TimeScope ts_small(ctx, std::string(tag) + "_lists_small");
+      k_nb_tile<kTcapSmall, 256, kTcapSmall, true><<<kGridSmall, 256, 0, st>>>(
+          g, qpos, recs, kRecInts, counters + kTilesSmall, rr, bscale, isort, lo, tq_dev, counters + kHeadSmall,
+          ch_small);
     }
     {
-      TimeScope ts(ctx, std::string(tag) + "_lists");
-      {
-        TimeScope t0(ctx, std::string(tag) + "_lists_small");
-        k_nb_tile<kTcapSmall, 256, kTcapSmall, true><<<256 * 4 * 2, 256, 0, st>>>(
-            g, qpos, recs, kRecInts, counters + 10, rr, 256.0f / rr, isort, lo, tq_dev, counters + 11,
-            ch_small);
-      }
-      {
-        TimeScope t1(ctx, std::string(tag) + "_lists_sparse");
-        k_nb_tile<512, 256, kTcapSparse, true><<<256 * 3 * 4, 256, 0, st>>>(
-            g, qpos, recs + (size_t)n * kRecInts, kRecInts, counters + 0, rr, 256.0f / rr, isort, lo, tq_dev, counters + 5,
-            ch_sparse);
-      }
-      {
-        TimeScope t2(ctx, std::string(tag) + "_lists_dense");
-        k_nb_tile<1024, 256, kTcapDense, false><<<256 * 2 * 4, 256, 0, st>>>(
-            g, qpos, recs + (size_t)(2 * n - 1) * kRecInts, -kRecInts, counters + 1, rr, 256.0f / rr, isort, lo, tq_dev,
-            counters + 7, ch_dense);
-      }
-      {
-        TimeScope t4(ctx, std::string(tag) + "_lists_wide");
-        if (ran_mids & 4) {
-          k_nb_wide<<<256 * 4, 256, 0, st>>>(g, qpos, recs, wq, counters + 16, rr, isort, lo, tq_dev, counters + 17);
-          check_launch("nblist wide tiles");
-        }
-      }
-      {
-        TimeScope t3(ctx, std::string(tag) + "_lists_query");
-        k_nb_query<kCapQuery, kBucketsQuery, false, kNtQuery, PFX_Q_WPE><<<256 * 4, kNtQuery, lds_q, st>>>(
-            g, single, counters + 2, rr, (float)kBucketsQuery / rr, isort, lo, tq_dev, counters + 4, nullptr,
-            counters + 8);
-        // lists of 4k-8k entries (dense clouds: ~14 % of the 10M-pt room's queries, 31 % of its
-        // entries) in two 72 KB workgroups per CU instead of the 16k tier's one (10M-pt dense
-        // variant: per-query lists 750 -> 650 ms, 1066 -> 968 ms per step; PFX_LIST_MID8=0 turns
-        // it off); the count stays on the device
-        if (use_mid8 && (ran_mids & 1)) launch_mid8();
-        // lists of up to 16k entries, one 144 KB workgroup per CU
-        if (ran_mids & 2) launch_mid();
-        // beyond 16k entries: once the scratch exists the launch is unconditional (count on the
-        // device); the first time, the readback below decides
-        if (hs.ptr) launch_huge();
-      }
-      check_launch("nblist lists");
+      TimeScope ts_sparse(ctx, std::string(tag) + "_lists_sparse");
+      k_nb_tile<512, 256, kTcapSparse, true><<<kGridSparse, 256, 0, st>>>(
+          g, qpos, recs + (size_t)n * kRecInts, kRecInts, counters + kTilesSparse, rr, bscale, isort, lo, tq_dev,
+          counters + kHeadSparse, ch_sparse);
     }
-    if (defer && attempt == 0) {  // consumers are launched before the readback (build_lists_check)
-      int64_t* d_nq_eff = B("nq_eff").as<int64_t>(1);
-      k_defer_gate<<<1, 64, 0, st>>>(counters, cursor, lo.cap, hs.ptr ? 1 : 0, ran_mids, G.oob, d_nq, d_nq_eff);
-      check_launch("k_defer_gate");
-      out.nq = n;
-      out.nq_dev = d_nq_eff;
-      out.qpos = qpos;
-      out.off = off;
-      out.cnt = cnt;
-      out.lg = lgs;
-      out.list = lo.list;
-      out.compact = compact;
-      out.list_cap = (int64_t)lo.cap;
-      out.skeys = G.skeys;
-      return;
+    {
+      TimeScope ts_dense(ctx, std::string(tag) + "_lists_dense");
+      k_nb_tile<1024, 256, kTcapDense, false><<<kGridDense, 256, 0, st>>>(
+          g, qpos, recs + (size_t)(2 * n - 1) * kRecInts, -kRecInts, counters + kTilesDense, rr, bscale, isort, lo,
+          tq_dev, counters + kHeadDense, ch_dense);
     }
-    read_back();
-    if (!(ran_mids & 4) && rb->cnt[16] > 0) {  // skipped wide tiles had work: rerun with every tier
-      note_mid_tiers(ctx, tag, rb->cnt);
-      ++ctx->stats[std::string(tag) + "_wide_reruns"];
-      continue;
+    {
+      TimeScope ts_wide(ctx, std::string(tag) + "_lists_wide");
+      if (ran & kRanWide) {
+        k_nb_wide<<<kGridWide, 256, 0, st>>>(g, qpos, recs, wq, counters + kTilesWide, rr, isort, lo, tq_dev,
+                                             counters + kHeadWide);
+        check_launch("nblist wide tiles");
+      }
     }
-    if ((!(ran_mids & 1) && rb->cnt[14] > 0) || (!(ran_mids & 2) && rb->cnt[12] > 0)) {
-      // a skipped per-query tier had work: run it and the tiers after it.  A launch that drained
-      // its queue left the head at count + gridDim (every workgroup's last fetch overshoots), so
-      // the head of each tier that already ran is first set back to the count it drained: the
-      // relaunch then takes exactly the entries the catch-up launches append
-      if (ran_mids & 2) PFX_HIP(hipMemcpyAsync(counters + 13, counters + 12, sizeof(int), hipMemcpyDeviceToDevice, st));
-      if (hs.ptr) PFX_HIP(hipMemcpyAsync(counters + 9, counters + 3, sizeof(int), hipMemcpyDeviceToDevice, st));
-      if (!(ran_mids & 1) && rb->cnt[14] > 0) launch_mid8();
-      launch_mid();
+    {
+      TimeScope ts_query(ctx, std::string(tag) + "_lists_query");
+      launch_4k();
+      if (ran & kRan8k) launch_8k();
+      if (ran & kRan16k) launch_16k();
+      // beyond 16k entries: once the scratch exists the launch is unconditional (count on the
+      // device); the first time, the readback decides
       if (hs.ptr) launch_huge();
-      read_back();
-      ++ctx->stats[std::string(tag) + "_tier_catchups"];
     }
-    note_mid_tiers(ctx, tag, rb->cnt);
-    if (!hs.ptr && rb->cnt[3] > 0) {  // very long lists, first time: allocate the scratch and sort them
-      huge_alloc(rb->cnt[3]);
-      launch_huge();
-      read_back();
-    } else if (hs.ptr && rb->cnt[3] > (int)huge_blocks() && huge_blocks() < (unsigned)kHugeBlocks) {
-      // more such lists than workgroups: more slices for the next build (this one has finished:
-      // the readback synchronised)
-      hs.release();
-      huge_alloc(rb->cnt[3]);
-    }
-    int* h_cnt = rb->cnt;
-    unsigned long long* h_cur = rb->cur;
-    const int64_t h_nq = rb->nq;
-    if (h_cnt[4] > 0)
-      throw Error(PFX_ERR_CAPACITY, std::string(tag) + ": a query has " + std::to_string(h_cnt[4]) +
-                                        " neighbours (> " + std::to_string(kCapHuge) + " supported)");
-    if (h_cur[0] > lo.cap) {  // list buffer too small: grow (no copy needed) and rebuild once
-      // The slot demand of a run is the entries + interleave padding (fixed by the input) + the
-      // unused arena tails (scheduling-dependent, at most one arena per launched workgroup), so
-      // this run's demand plus the tail bound always fits the rebuild.
-      const size_t tails = (size_t)(256 * 4 * 2 + 256 * 3 * 4 + 256 * 2 * 4) * kArena +
-                           (size_t)(256 * 4 + 256 * 4 + 256 * 2 + 256 + kHugeBlocks) * kArenaQuery;
-      lb.release();
-      lb.get(sizeof(uint32_t) * ((size_t)h_cur[0] + tails + ((size_t)1 << 20)));
-      continue;
-    }
-    out.nq = h_nq;
-    out.total = (int64_t)h_cur[1];
-    out.long_total = (int64_t)h_cur[2];
-    out.long_nq = (int64_t)h_cur[3];
-    out.slots = (int64_t)h_cur[0];
+    check_launch("nblist lists");
+  }
+
+  // a deferred build's end: the consumers' query count gated on the device, `out` an upper bound
+  void defer_to_check(int ran, NbLists& out) {
+    int64_t* d_nq_eff = buf("nq_eff").as<int64_t>(1);
+    k_defer_gate<<<1, 64, 0, st>>>(counters, cursor, list_words(), hs.ptr ? 1 : 0, ran, G.oob, d_nq, d_nq_eff);
+    check_launch("k_defer_gate");
+    point(out);
+    out.nq = n;
+    out.nq_dev = d_nq_eff;
+  }
+
+  // step 4: the readback, and what the lists lack by it given the skippable kernels that ran
+  const ListsRb* read_back() { return pfx::read_back(ctx, counters, cursor, d_nq, nullptr); }
+  int lack(const ListsRb* rb, int ran) const {
+    return lists_lack(rb->cnt, rb->cur[0], list_words(), hs.ptr != nullptr, ran, rb->oob);
+  }
+
+  // step 5: a skipped per-query tier had work: run it and the tiers after it.  A launch that
+  // drained its queue left the head at count + gridDim (every workgroup's last fetch overshoots),
+  // so the head of each tier that already ran is first set back to the count it drained: the
+  // relaunch then takes exactly the entries the catch-up launches append
+  void catch_up(int lacking, int ran) {
+    auto rewind = [&](Counter head, Counter count) {
+      PFX_HIP(hipMemcpyAsync(counters + head, counters + count, sizeof(int), hipMemcpyDeviceToDevice, st));
+    };
+    if (ran & kRan16k) rewind(kHead16k, kWork16k);
+    if (hs.ptr) rewind(kHeadHuge, kWorkHuge);
+    if (lacking & kRan8k) launch_8k();
+    launch_16k();
+    if (hs.ptr) launch_huge();
+  }
+
+  // step 6: the huge tier's scratch for `count` lists (at least a workgroup per CU)
+  void huge_alloc(int count) { hs.get(kHugeSlice * (size_t)std::min(kGridHugeMax, std::max(kCUs, count))); }
+
+  // step 7: list buffer too small: grow (no copy needed) for a rebuild.  The slot demand of a
+  // run is the entries + interleave padding (fixed by the input) + the unused arena tails
+  // (scheduling-dependent, at most one arena per launched workgroup), so this run's demand plus
+  // the tail bound always fits the rebuild.
+  void regrow(unsigned long long demand) {
+    lb.release();
+    lb.get(sizeof(uint32_t) * ((size_t)demand + kArenaTails + ((size_t)1 << 20)));
+  }
+
+  // step 8 (with publish): the device half of `out`
+  void point(NbLists& out) const {
     out.qpos = qpos;
     out.off = off;
     out.cnt = cnt;
     out.lg = lgs;
-    out.list = lo.list;
-    out.compact = compact;
-    out.list_cap = (int64_t)lo.cap;
+    out.list = static_cast<const uint32_t*>(lb.ptr);
+    out.compact = compact != 0;
+    out.list_cap = (int64_t)list_words();
     out.skeys = G.skeys;
-    ctx->stats[std::string(tag) + "_tiles_sparse"] = h_cnt[0];
-    ctx->stats[std::string(tag) + "_tiles_dense"] = h_cnt[1];
-    ctx->stats[std::string(tag) + "_single"] = h_cnt[2];
-    ctx->stats[std::string(tag) + "_huge"] = h_cnt[3];
-    ctx->stats[std::string(tag) + "_mid"] = h_cnt[12];
-    ctx->stats[std::string(tag) + "_wide"] = h_cnt[16];
-    ctx->stats[std::string(tag) + "_mid8"] = h_cnt[14];
-    ctx->stats[std::string(tag) + "_slots"] = (int64_t)h_cur[0];  // list words reserved (entries + padding + arena tails)
-    ctx->stats[std::string(tag) + "_list_words"] = (int64_t)lo.cap;
-#ifdef PFX_SHOT_PROFILE
-    {
-      unsigned long long pr[28];
-      PFX_HIP(hipMemcpyFromSymbol(pr, HIP_SYMBOL(g_tile_prof), sizeof(pr)));
-      fprintf(stderr, "%s wave_sort cycles (wave 0): count %llu scan %llu scatter %llu rank %llu\n", tag, pr[8],
-              pr[9], pr[10], pr[11]);
-      fprintf(stderr, "%s tile cycles: sparse stage %llu test %llu sort %llu write %llu | dense - %llu test %llu "
-              "sort %llu write %llu | small - %llu test %llu sort %llu write %llu (cumulative)\n", tag, pr[0], pr[1], pr[2],
-              pr[3], pr[4], pr[5], pr[6], pr[7], pr[16], pr[17], pr[18], pr[19]);
-      fprintf(stderr, "%s query cycles: test %llu sort+write %llu | entries %llu candidates %llu\n", tag, pr[20],
-              pr[21], pr[22], pr[23]);
-      fprintf(stderr, "%s query 4k-tier phases: scan %llu scatter %llu rank+write %llu | list-mode items %llu\n", tag,
-              pr[24], pr[25], pr[26], pr[27]);
-      unsigned long long pw[12];
-      PFX_HIP(hipMemcpyFromSymbol(pw, HIP_SYMBOL(g_tile_prof2), sizeof(pw)));
-      fprintf(stderr, "%s wave cycles (sum over waves): small sort %llu sortwait %llu staging %llu listwrite %llu | "
-              "sparse %llu %llu %llu %llu | dense %llu %llu %llu %llu\n", tag, pw[0], pw[1], pw[2], pw[3], pw[4], pw[5],
-              pw[6], pw[7], pw[8], pw[9], pw[10], pw[11]);
-      static const unsigned long long zw[12] = {};
-      PFX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_tile_prof2), zw, sizeof(zw)));
-      static const unsigned long long zero[24] = {};
-      PFX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_tile_prof), zero, sizeof(zero)));
+  }
+};
+
+}  // namespace
+
+bool build_lists_check(pfx_ctx* ctx, const Grid& G, NbLists& out, const char* tag) {
+  auto B = [&](const char* what) -> DevBuf& { return ctx->bufs[bname(tag, what)]; };
+  const ListsRb* rb = read_back(ctx, B("counters").ptr, B("cursor").ptr, B("nq").ptr, G.oob);
+  const size_t words = B("list").bytes / sizeof(uint32_t);
+  const int ran = (int)ctx->stats[std::string(tag) + "_ran_mid_tiers"];
+  const int lacking = lists_lack(rb->cnt, rb->cur[0], words, B("scratch").ptr != nullptr, ran, rb->oob);
+  // speculative grid too small, list buffer too small, first very long lists
+  if (lacking & (kLackGrid | kLackBuffer | kLackScratch)) return false;
+  // The hints are updated exactly here -- after the grid, buffer and scratch checks, before the
+  // skipped-tier check: a build failing the former leaves them as they were, one failing the
+  // latter has already revived the hint of the tier it missed, and either changes which kernels
+  // the rebuild's first attempt launches.
+  note_mid_tiers(ctx, tag, rb->cnt);
+  if (lacking) return false;  // a skipped tier had work
+  if (rb->cnt[kOverCap] > 0) throw_over_cap(tag, rb->cnt[kOverCap]);
+  publish(ctx, tag, *rb, words, out);
+  return true;
+}
+
+void build_lists(pfx_ctx* ctx, const Grid& G, const uint8_t* mask, double radius, bool sorted, NbLists& out,
+                 const char* tag, bool defer, int want, bool compact, bool gate) {
+  out = NbLists();
+  if (G.n == 0) return;
+  if (G.n >= (int64_t(1) << 28))
+    throw Error(PFX_ERR_CAPACITY, std::string(tag) + ": neighbour lists support < 2^28 points");
+  ListBuild b(ctx, G, tag, radius, sorted, compact);
+  b.setup(mask, want);
+  if (gate && ctx->lists_gate) {  // pfx_normals_gate_dev: the caller's event, once, right before the list kernels
+    // (after the list set-up above, which therefore overlaps the gated stage)
+    PFX_HIP(hipStreamWaitEvent(b.st, ctx->lists_gate, 0));
+    ctx->lists_gate = nullptr;
+  }
+  for (int attempt = 0; attempt < 3; ++attempt) {
+    if (attempt) b.reset_for_retry();
+    // (see wanted_tiers; a retry launches every kernel)
+    int ran = attempt ? kRanAll : wanted_tiers(ctx, tag);
+    ctx->stats[std::string(tag) + "_ran_mid_tiers"] = ran;
+    b.launch_lists(ran);
+    if (defer && attempt == 0) {  // consumers are launched before the readback (build_lists_check)
+      b.defer_to_check(ran, out);
+      return;
     }
+    const ListsRb* rb = b.read_back();
+    int lacking = b.lack(rb, ran);
+    if (lacking & kRanWide) {  // skipped wide tiles had work: retry with every kernel
+      note_mid_tiers(ctx, tag, rb->cnt);
+      ++ctx->stats[std::string(tag) + "_wide_reruns"];
+      continue;
+    }
+    if (lacking & (kRan8k | kRan16k)) {
+      b.catch_up(lacking, ran);
+      ran = kRanAll;  // (a tier not launched even now had no work)
+      rb = b.read_back();
+      lacking = b.lack(rb, ran);
+      ++ctx->stats[std::string(tag) + "_tier_catchups"];
+    }
+    note_mid_tiers(ctx, tag, rb->cnt);
+    const int n_huge = rb->cnt[kWorkHuge];
+    if (lacking & kLackScratch) {  // very long lists, first time: allocate the scratch and sort them
+      b.huge_alloc(n_huge);
+      b.launch_huge();
+      rb = b.read_back();
+      lacking = b.lack(rb, ran);
+    } else if (b.hs.ptr && n_huge > (int)b.huge_blocks() && b.huge_blocks() < (unsigned)kGridHugeMax) {
+      // more such lists than workgroups: more slices for the next build (this one has finished:
+      // the readback synchronised)
+      b.hs.release();
+      b.huge_alloc(n_huge);
+    }
+    if (rb->cnt[kOverCap] > 0) throw_over_cap(tag, rb->cnt[kOverCap]);
+    if (lacking & kLackBuffer) {  // rebuild once in a larger buffer
+      b.regrow(rb->cur[0]);
+      continue;
+    }
+    b.point(out);
+    publish(ctx, tag, *rb, b.list_words(), out);
+#ifdef PFX_SHOT_PROFILE
+    report_probes(tag);
 #endif
     return;
   }

@@ -139,7 +139,7 @@ def _wide_blob(rng):
 
 def test_list_tier_hints_every_path_fresh_context():
     """The 4k-8k / 8k-16k per-query list tiers and the wide-tile kernel launch only while a recent
-    build of the (context, tag) had work for them (pfx_nblist.hip mid_tier_wanted).  On a fresh
+    build of the (context, tag) had work for them (pfx_nblist.hip wanted_tiers).  On a fresh
     context, once hints have decayed (17 builds without such lists), a cloud that needs the skipped
     kernels must still come out exact on every path:
       * the 8k-16k tier skipped while the wide tiles and the 4k-8k tier run: the non-deferred
@@ -204,6 +204,18 @@ def test_list_tier_hints_every_path_fresh_context():
         for _ in range(17):
             lists_only(px, py, pz)
         g = c.normals(ex, ey, ez, 0.05)            # deferred build (normals_dev): check + exact rebuild
+        for a, b in zip(g, ref):
+            assert _nan_aware_equal(a, b)
+        # a deferred build the check accepts as it stands publishes the same stats as a synchronous
+        # one.  First a synchronous build of the same cloud without its 4k-8k blob (the same
+        # bounds, so the speculative grid still holds) sets `normals_mid8` to 0; the hints stay alive
+        nx_, ny_, nz_ = _xyz(sparse, dense, mid, huge)
+        lists_only(nx_, ny_, nz_)
+        assert stat("mid8") == 0 and stat("mid") > 0
+        reruns = stat("speculative_reruns")
+        g = c.normals(ex, ey, ez, 0.05)            # deferred build, every tier launched, no rebuild
+        assert stat("speculative_reruns") == reruns
+        assert c.stat("normals_mid8") > 0
         for a, b in zip(g, ref):
             assert _nan_aware_equal(a, b)
 
