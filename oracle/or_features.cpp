@@ -196,6 +196,34 @@ int orc_normals(const float* x, const float* y, const float* z, i64 n, double r,
   return 0;
 }
 
+// orc_normals for the rows[0..nrows) only (out arrays of nrows entries, in rows' order): the same
+// loop body, so a test can check very long lists without paying for every point of the cloud.
+int orc_normals_rows(const float* x, const float* y, const float* z, i64 n, double r, float vpx,
+                     float vpy, float vpz, const i64* rows, i64 nrows, float* nx, float* ny, float* nz,
+                     float* curv, int nthreads) {
+  for (i64 j = 0; j < nrows; ++j)
+    if (rows[j] < 0 || rows[j] >= n) return 1;
+  NeighborGrid g;
+  g.build(x, y, z, n, r);
+#ifdef _OPENMP
+  if (nthreads > 0) omp_set_num_threads(nthreads);
+#endif
+#pragma omp parallel
+  {
+    std::vector<int> nb;
+    std::vector<float> dd;
+#pragma omp for schedule(dynamic, 1)
+    for (i64 j = 0; j < nrows; ++j) {
+      i64 i = rows[j];
+      g.radius(x[i], y[i], z[i], r, nb, dd);
+      float o[4];
+      pointNormal(x, y, z, nb, x[i], y[i], z[i], vpx, vpy, vpz, o);
+      nx[j] = o[0]; ny[j] = o[1]; nz[j] = o[2]; curv[j] = o[3];
+    }
+  }
+  return 0;
+}
+
 // FPFHEstimation::computeFeature (non-OMP class: single-threaded, evaluation.cpp:597).
 // same_as_surface != 0 reproduces PCL's "input_ == surface_ and all indices" branch.
 // spfh_rows_out (optional, |S| x 33) and n_spfh_out expose the SPFH table for debugging.

@@ -33,8 +33,13 @@ constexpr int kHistCopies = 16;  // SPFH per-wave counter copies
 // PCL 1.7 `acos (fabs (a1)) > acos (fabs (a2))` (double acos, correctly rounded by glibc):
 // acos is strictly decreasing and distinct floats >= 2^-26 map to distinct rounded values, so
 // the test is |a1| < |a2|; below 2^-26 acos(x) rounds as H + (L - x), pi/2 = H + L.
+// |a| > 1 (a normal parallel to the pair's direction, the float quotient rounded past 1): acos is
+// NaN and PCL's comparison false -- no swap, whichever side it is on.  (The fast path never bins
+// such a pair: |f3| is the larger |angle|, and within 1.5e-6 of 1 its bin map is within tolerance
+// of the edge at 0 or kBins; a pair whose v_norm is 0 is not binned there either.)
 __device__ __forceinline__ bool acos_greater(float a1, float a2) {
   float x1 = fabsf(a1), x2 = fabsf(a2);
+  if (x1 > 1.0f || x2 > 1.0f) return false;
   if (x1 >= 1.4901161e-08f || x2 >= 1.4901161e-08f) return x1 < x2;
   const double H = 1.5707963267948966, L = 6.123233995736766e-17;
   return (H + (L - (double)x1)) > (H + (L - (double)x2));
@@ -211,11 +216,9 @@ __device__ __forceinline__ bool pair_bins_fast(f3 p1, f3 n1, f3 p2, f3 n2, int& 
   }
   const f3 v = cross3(dp, n1c);
   const float sv = sqn4(v);
-  if (sv == 0.0f) {  // v_norm == 0 in pair_bins
-    h1 = bin_of(f1_scaled(0.0));
-    h2 = h3 = bin_of((double)kBins * ((0.0 + 1.0) * 0.5));
-    return true;
-  }
+  // (v_norm == 0 in pair_bins: the chosen normal is parallel to dp, so an |angle| may have rounded
+  // past 1 and the swap above may not be PCL's -- the exact path decides)
+  if (sv == 0.0f) return false;
   const f3 vh = scale3(v, __builtin_amdgcn_rsqf(sv));
   const f3 w = cross3(n1c, vh);
   const float f2a = dot4(vh, n2c);
@@ -316,8 +319,10 @@ __device__ __forceinline__ void pair_bins_fast2(f3 p1, f3 n1, bool n1fin, const 
     const bool k1 = bin_fast_nb(b1[c], tol1[c], a1);
     const bool k2 = bin_fast_nb(b2[c], 4e-6f * 0.5f * kBins + kBinMapSlack, a2);
     const bool k3 = bin_fast_nb(b3[c], 1e-6f * 0.5f * kBins + kBinMapSlack, a3);
-    // f4 == 0, or v_norm == 0, in pair_bins: the zero-feature bins
-    const bool zero = (s4[c] == 0.0f) | (live[c] & (sv[c] == 0.0f));
+    // f4 == 0 in pair_bins: the zero-feature bins.  (v_norm == 0, the chosen normal parallel to dp:
+    // f2 is NaN here, so k2 fails and the exact path takes the pair -- an |angle| may have
+    // rounded past 1 there, and the swap above is then not PCL's.)
+    const bool zero = s4[c] == 0.0f;
     ok[c] = zero | (live[c] & big[c] & k1 & k2 & k3);
     h1[c] = zero ? bz1 : a1;
     h2[c] = zero ? bz : a2;

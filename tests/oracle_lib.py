@@ -87,6 +87,18 @@ def normals(x, y, z, r, vp=(0.0, 0.0, 0.0), threads=0):
     return out[0], out[1], out[2], out[3]
 
 
+def normals_rows(x, y, z, r, rows, vp=(0.0, 0.0, 0.0), threads=0):
+    """normals() of the given rows only: (nx, ny, nz, curvature), one entry per row, in rows' order."""
+    x, y, z = map(_f32, (x, y, z))
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    out = np.empty((4, len(rows)), dtype=np.float32)
+    rc = lib().orc_normals_rows(_p(x), _p(y), _p(z), _i64(len(x)), ctypes.c_double(r), ctypes.c_float(vp[0]),
+                                ctypes.c_float(vp[1]), ctypes.c_float(vp[2]), _p(rows, _i64p), _i64(len(rows)),
+                                _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), ctypes.c_int(threads))
+    assert rc == 0, rc
+    return out[0], out[1], out[2], out[3]
+
+
 def fpfh(sx, sy, sz, nx, ny, nz, qx, qy, qz, r, same_as_surface=False, threads=0):
     sx, sy, sz, nx, ny, nz, qx, qy, qz = map(_f32, (sx, sy, sz, nx, ny, nz, qx, qy, qz))
     nq = len(qx)

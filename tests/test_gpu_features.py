@@ -330,6 +330,32 @@ def test_fpfh_deferred_pair_queue_overflow(ctx, monkeypatch):
     assert _nan_aware_equal(g, O.fpfh(x, y, z, nx, ny, nz, x[q], y[q], z[q], 0.08))
 
 
+def test_fpfh_pair_angle_rounded_past_one(ctx):
+    """computePairFeatures swaps the pair when acos(|angle1|) > acos(|angle2|), angle = n . dp / |dp|
+    in float.  A normal parallel to dp can round |angle| past 1: acos is NaN, the comparison false
+    and PCL does not swap, whichever side the NaN is on.  Radial normals around one point put
+    hundreds of such pairs into that point's SPFH row."""
+    rng = np.random.default_rng(12)
+    c = np.array([0.4, 0.3, 1.1], np.float32)
+    p = (c + rng.uniform(-0.02, 0.02, (1500, 3))).astype(np.float32)
+    dp = p - c
+    f4 = np.sqrt((dp[:, 0] * dp[:, 0] + dp[:, 2] * dp[:, 2]) + (dp[:, 1] * dp[:, 1] + np.float32(0)))
+    nrm = dp / f4[:, None]                                            # float32 throughout
+    angle = ((nrm[:, 0] * dp[:, 0] + nrm[:, 2] * dp[:, 2]) + (nrm[:, 1] * dp[:, 1] + np.float32(0))) / f4
+    assert angle.dtype == np.float32 and (np.abs(angle) > 1).sum() > 100
+    pts = np.concatenate([c[None], p])
+    nrm = np.concatenate([np.array([[0.0, 0.6, 0.8]], np.float32), nrm])
+    x, y, z = pts[:, 0].copy(), pts[:, 1].copy(), pts[:, 2].copy()
+    nx, ny, nz = nrm[:, 0].copy(), nrm[:, 1].copy(), nrm[:, 2].copy()
+    q = np.array([0, 1, 700, 1500])
+    g = ctx.fpfh(x, y, z, nx, ny, nz, x[q], y[q], z[q], 0.05)
+    o = O.fpfh(x, y, z, nx, ny, nz, x[q], y[q], z[q], 0.05)
+    assert _nan_aware_equal(g, o)
+    g = ctx.fpfh(x, y, z, nx, ny, nz, None, None, None, 0.05, same_as_surface=True)
+    o = O.fpfh(x, y, z, nx, ny, nz, x, y, z, 0.05, same_as_surface=True)
+    assert _nan_aware_equal(g, o)
+
+
 def _shell(n, radius, seed, centre=(0.3, -0.2, 1.5)):
     """n points on a sphere shell of the given radius (float32 SoA) plus outward normals."""
     rng = np.random.default_rng(seed)
