@@ -21,6 +21,8 @@
  *                          Features<T>::compute (features.h:175-196, evaluation.cpp:593-612)
  *   pfx_shot*           <- SHOTEstimationOMP<PointXYZRGB,Normal,SHOT352>::compute
  *                          (features.h:175-196, evaluation.cpp:766-785)
+ *   pfx_pfh*            <- PFHEstimation<PointXYZRGB,Normal,PFHSignature125>::compute
+ *                          (features.h:175-196, evaluation.cpp:676-695)
  *   pfx_range_image_planar* <- RangeImagePlanar::createFromPointCloudWithFixedSize
  *                          (keypoints.h:212-216, tools.h:61-77)
  *   pfx_narf_keypoints* <- RangeImageBorderExtractor + NarfKeypoint::compute
@@ -124,7 +126,7 @@ pfx_status pfx_ctx_set_stream(pfx_ctx* ctx, void* hip_stream);
 pfx_status pfx_ctx_use_own_stream(pfx_ctx* ctx);
 void* pfx_ctx_get_stream(pfx_ctx* ctx);
 /* Frees every device scratch buffer of ctx (grids, neighbour lists, the rarely used overflow
- * scratch of the list builder and the FPFH weighting, NARF images) after synchronising its
+ * scratch of the list builder, the FPFH weighting and PFH, NARF images) after synchronising its
  * stream; the next call reallocates what it needs.  Held state (lists kept for
  * pfx_normals_chains_dev / pfx_fpfh_after_normals_dev, prepared FPFH grids) is dropped. */
 pfx_status pfx_ctx_trim(pfx_ctx* ctx);
@@ -304,6 +306,26 @@ pfx_status pfx_shot_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, cons
                         int64_t n_surface, const float* d_qx, const float* d_qy,
                         const float* d_qz, int64_t nq, double radius, float* d_desc,
                         float* d_rf);
+
+/* ---- PFH-125: PFHEstimation (surface + normals, queries = input cloud) ---------------- */
+/* out: nq x 125 row-major (PFHSignature125::histogram): every pair of a query's radius
+ * neighbourhood binned 5 x 5 x 5, each hit adding 100 / (k (k - 1) / 2); a non-finite query or
+ * an empty neighbourhood gives a NaN row.  PFH has no input == surface branch, so there is no
+ * same_as_surface flag; the feature cache (use_cache_) and k-NN search are not supported. */
+pfx_status pfx_pfh(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz,
+                   const float* snx, const float* sny, const float* snz, int64_t n_surface,
+                   const float* qx, const float* qy, const float* qz, int64_t nq,
+                   double radius, float* out);
+/* Device pointers, stream-ordered on the ctx stream, no host synchronisation.  A query with more
+ * than 65535 neighbours (its pair count no longer fits 32 bits) gets a NaN row and
+ * PFX_ERR_CAPACITY from the next pfx_ctx_synchronize / pfx_ctx_last_stats on ctx.  Statistics of
+ * the last call: "pfh_pairs" (sum over the queries of k (k - 1) / 2), "pfh_kmax", "pfh_global"
+ * (queries whose neighbourhood exceeded "pfh_cap_lds", the LDS staging capacity, and took the
+ * global-scratch pass; "pfh_cap_lds" itself can be read from a new ctx). */
+pfx_status pfx_pfh_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                       const float* d_snx, const float* d_sny, const float* d_snz,
+                       int64_t n_surface, const float* d_qx, const float* d_qy,
+                       const float* d_qz, int64_t nq, double radius, float* d_out);
 
 /* ---- range image + NARF keypoints ---------------------------------------------------- */
 /* out_points: width*height x 4 floats {x, y, z, range} (PointWithRange); unobserved pixels

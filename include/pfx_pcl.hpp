@@ -7,7 +7,7 @@
 //                                                       probed with dynamic_pointer_cast),
 //                                                       search::KdTree, setRadiusSearch, compute
 //   include/pcl_feature_extraction/tools.h:22-32        NormalEstimationOMP
-//   src/evaluation.cpp:593-612, :766-785                FPFHEstimation, SHOTEstimationOMP
+//   src/evaluation.cpp:593-612, :676-695, :766-785      FPFHEstimation, PFHEstimation, SHOTEstimationOMP
 //   include/pcl_feature_extraction/features.h:224-273   KdTreeFLANN<FeatureT>::nearestKSearch,
 //                                                       Correspondence(s), boost::thread / ref
 // This header provides those names in namespace pcl (plus the minimal Eigen subset the calls
@@ -185,6 +185,7 @@ struct alignas(16) PointXYZI {
   float pad_[3] = {0, 0, 0};
 };
 struct FPFHSignature33 { float histogram[33]; };
+struct PFHSignature125 { float histogram[125]; };
 struct SHOT352 { float descriptor[352]; float rf[9]; };
 struct ReferenceFrame { float x_axis[3], y_axis[3], z_axis[3]; };
 
@@ -360,6 +361,39 @@ class FPFHEstimation : public FeatureFromNormals<PointInT, PointNT, PointOutT> {
     for (size_t i = 0; i < nq; ++i) {
       for (int b = 0; b < 33; ++b) out.points[i].histogram[b] = h[i * 33 + b];
       if (std::isnan(h[i * 33])) out.is_dense = false;
+    }
+  }
+};
+
+// PFHEstimation<In, Normal, PFHSignature125> (evaluation.cpp:680); the feature cache
+// (setUseInternalCache) is not on the accelerated path -- the reference never enables it
+template <typename PointInT, typename PointNT, typename PointOutT = PFHSignature125>
+class PFHEstimation : public FeatureFromNormals<PointInT, PointNT, PointOutT> {
+ public:
+  typedef std::shared_ptr<PFHEstimation<PointInT, PointNT, PointOutT> > Ptr;
+  PFHEstimation() { this->name_ = "PFHEstimation"; }
+
+ protected:
+  void computeFeature(PointCloud<PointOutT>& out) override {
+    const PointCloud<PointInT>& surf = this->surface();
+    if (!this->normals_ || this->normals_->size() != surf.size()) {
+      PCL_ERROR("[pcl::PFHEstimation::compute] normals missing or not matching the surface\n");
+      return;
+    }
+    const detail::SoA s = detail::soa_xyz(surf), nrm = detail::soa_normals(*this->normals_);
+    const detail::SoA q = detail::soa_xyz(*this->input_);
+    const size_t nq = this->input_->size();
+    std::vector<float> h(nq * 125);
+    if (!detail::ok(pfx_pfh(detail::context(), s.x.data(), s.y.data(), s.z.data(), nrm.x.data(), nrm.y.data(),
+                            nrm.z.data(), (int64_t)surf.size(), q.x.data(), q.y.data(), q.z.data(), (int64_t)nq,
+                            this->search_radius_, h.data()),
+                    "PFHEstimation"))
+      return;
+    out.resize(nq);
+    out.is_dense = true;
+    for (size_t i = 0; i < nq; ++i) {
+      for (int b = 0; b < 125; ++b) out.points[i].histogram[b] = h[i * 125 + b];
+      if (std::isnan(h[i * 125])) out.is_dense = false;
     }
   }
 };
@@ -739,6 +773,7 @@ namespace detail {
 template <typename T> struct DescriptorLayout;
 template <> struct DescriptorLayout<FPFHSignature33> { static constexpr int dim = 33, stride = 33; };
 template <> struct DescriptorLayout<SHOT352> { static constexpr int dim = 352, stride = 361; };
+template <> struct DescriptorLayout<PFHSignature125> { static constexpr int dim = 125, stride = 125; };
 }  // namespace detail
 
 // KdTreeFLANN<FeatureT> with nearestKSearch(k = 1), as the reference uses it (features.h:258-272):

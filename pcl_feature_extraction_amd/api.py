@@ -180,6 +180,15 @@ class Context:
                                        _ptr(qx), _ptr(qy), _ptr(qz), nq, float(r), _ptr(desc), _ptr(rf)))
         return desc, rf
 
+    def pfh(self, sx, sy, sz, nx, ny, nz, qx, qy, qz, r):
+        """PFHEstimation (pfx_pfh): (nq, 125) float32, NaN rows for queries without neighbours."""
+        sx, sy, sz, nx, ny, nz, qx, qy, qz = map(_f32, (sx, sy, sz, nx, ny, nz, qx, qy, qz))
+        nq = len(qx)
+        out = np.empty((nq, 125), dtype=np.float32)
+        self._check(self._lib.pfx_pfh(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(nx), _ptr(ny), _ptr(nz), len(sx),
+                                      _ptr(qx), _ptr(qy), _ptr(qz), nq, float(r), _ptr(out)))
+        return out
+
     def range_image_planar(self, x, y, z, cam=None):
         cam = cam or camera()
         x, y, z = map(_f32, (x, y, z))
@@ -295,6 +304,13 @@ class Context:
         self._check(self._lib.pfx_shot_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(nx), _ptr(ny), _ptr(nz),
                                            sx.numel(), _ptr(qx), _ptr(qy), _ptr(qz), qx.numel(), float(r),
                                            _ptr(desc), _ptr(rf)))
+
+    def pfh_dev(self, sx, sy, sz, nx, ny, nz, qx, qy, qz, r, out):
+        """pfx_pfh_dev: out is an (nq, 125) float32 device tensor; no host synchronisation (a
+        neighbourhood beyond capacity is reported by the next synchronize())."""
+        self._check(self._lib.pfx_pfh_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(nx), _ptr(ny), _ptr(nz),
+                                          sx.numel(), _ptr(qx), _ptr(qy), _ptr(qz), qx.numel(), float(r),
+                                          _ptr(out)))
 
     def narf_keypoints_dev(self, x, y, z, params=None, cam=None, cap=1 << 20):
         cam = cam or camera()

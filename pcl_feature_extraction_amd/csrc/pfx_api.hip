@@ -105,6 +105,7 @@ pfx_status pfx_ctx_create(int device, pfx_ctx** out) {
     ctx->device = device;
     PFX_HIP(hipSetDevice(device));
     ctx->on_own_stream = true;  // created on first use (check_ctx)
+    ctx->stats["pfh_cap_lds"] = pfx::pfh_cap_lds();
     *out = ctx;
     return PFX_OK;
   } catch (const Error& e) {
@@ -133,6 +134,7 @@ void pfx_ctx_destroy(pfx_ctx* ctx) {
   if (ctx->host_rb) (void)hipHostFree(ctx->host_rb);
   if (ctx->host_scratch) (void)hipHostFree(ctx->host_scratch);
   if (ctx->fpfh_rb_mem) (void)hipHostFree(ctx->fpfh_rb_mem);
+  if (ctx->pfh_rb_mem) (void)hipHostFree(ctx->pfh_rb_mem);
   delete ctx;
 }
 
@@ -177,6 +179,7 @@ pfx_status pfx_ctx_trim(pfx_ctx* ctx) {
   ctx->lists_gate = nullptr;  // a borrowed event the next call must not wait on
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   pfx::fpfh_resolve(ctx);
+  pfx::pfh_resolve(ctx);
   pfx::narf_release(ctx);
   pfx::normals_release(ctx);
   pfx::keypoints_release(ctx);
@@ -196,6 +199,7 @@ pfx_status pfx_ctx_synchronize(pfx_ctx* ctx) {
   check_ctx(ctx);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   pfx::fpfh_resolve(ctx);  // deferred statistics / capacity errors of the stream-ordered calls
+  pfx::pfh_resolve(ctx);
   PFX_API_END(ctx)
 }
 
@@ -237,9 +241,10 @@ pfx_status pfx_ctx_kernel_time(pfx_ctx* ctx, const char* name, double* total_ms,
 pfx_status pfx_ctx_last_stats(pfx_ctx* ctx, const char* what, int64_t* value) {
   PFX_API_BEGIN
   if (!ctx || !what || !value) throw Error(PFX_ERR_INVALID, "null argument");
-  if (ctx->fpfh_pending) {
+  if (ctx->fpfh_pending || ctx->pfh_pending) {
     PFX_HIP(hipStreamSynchronize(ctx->stream));
     pfx::fpfh_resolve(ctx);
+    pfx::pfh_resolve(ctx);
   }
   auto it = ctx->stats.find(what);
   if (it == ctx->stats.end()) throw Error(PFX_ERR_INVALID, std::string("unknown stat ") + what);
@@ -568,6 +573,43 @@ pfx_status pfx_shot(pfx_ctx* ctx, const float* sx, const float* sy, const float*
     PFX_HIP(hipMemcpyAsync(rf, drf, sizeof(float) * nq * 9, hipMemcpyDeviceToHost, ctx->stream));
   }
   PFX_HIP(hipStreamSynchronize(ctx->stream));
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_pfh_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz, const float* d_snx,
+                       const float* d_sny, const float* d_snz, int64_t n_surface, const float* d_qx,
+                       const float* d_qy, const float* d_qz, int64_t nq, double radius, float* d_out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!d_out || !d_qx || !d_qy || !d_qz)) ||
+      (n_surface && (!d_sx || !d_sy || !d_sz || !d_snx || !d_sny || !d_snz)))
+    throw Error(PFX_ERR_INVALID, "pfh: invalid arguments");
+  pfx::pfh_dev(ctx, d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, nq, radius, d_out);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_pfh(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
+                   const float* sny, const float* snz, int64_t n_surface, const float* qx, const float* qy,
+                   const float* qz, int64_t nq, double radius, float* out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!out || !qx || !qy || !qz)) ||
+      (n_surface && (!sx || !sy || !sz || !snx || !sny || !snz)))
+    throw Error(PFX_ERR_INVALID, "pfh: invalid arguments");
+  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
+  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
+  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
+  float* dnx = stage_in(ctx, "in_nx", snx, n_surface);
+  float* dny = stage_in(ctx, "in_ny", sny, n_surface);
+  float* dnz = stage_in(ctx, "in_nz", snz, n_surface);
+  float* dqx = stage_in(ctx, "in_qx", qx, nq);
+  float* dqy = stage_in(ctx, "in_qy", qy, nq);
+  float* dqz = stage_in(ctx, "in_qz", qz, nq);
+  float* dout = ctx->buf("out_pfh").as<float>(nq * 125 + 1);
+  pfx::pfh_dev(ctx, dsx, dsy, dsz, dnx, dny, dnz, n_surface, dqx, dqy, dqz, nq, radius, dout);
+  if (nq) PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * 125, hipMemcpyDeviceToHost, ctx->stream));
+  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  pfx::pfh_resolve(ctx);  // the host API reports at once
   PFX_API_END(ctx)
 }
 

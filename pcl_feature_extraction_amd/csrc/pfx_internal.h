@@ -156,6 +156,9 @@ struct pfx_ctx {
     if (!fpfh_rb_mem) PFX_HIP(hipHostMalloc(&fpfh_rb_mem, sizeof(pfx::FpfhReadback), hipHostMallocDefault));
     return static_cast<pfx::FpfhReadback*>(fpfh_rb_mem);
   }
+  // pfh_dev's statistics / sticky error word, the same way (pfx::pfh_resolve)
+  void* pfh_rb_mem = nullptr;
+  bool pfh_pending = false;
   // one side stream + fork/join events (normal estimation's long-list chains), created on first use
   hipStream_t side = nullptr;
   hipEvent_t fork_ev[2] = {nullptr, nullptr};
@@ -307,6 +310,12 @@ void fpfh_prepare_queries_dev(pfx_ctx* ctx, const float* sx, const float* sy, co
 void shot_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
               const float* sny, const float* snz, int64_t ns, const float* qx, const float* qy,
               const float* qz, int64_t nq, double r, float* desc, float* rf);
+// PFH-125 (pfx_pfh.hip): stream-ordered, no host synchronisation; pfh_resolve as fpfh_resolve
+void pfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
+             const float* sny, const float* snz, int64_t ns, const float* qx, const float* qy,
+             const float* qz, int64_t nq, double r, float* out);
+void pfh_resolve(pfx_ctx* ctx);
+int pfh_cap_lds();  // neighbours a query's workgroup stages in LDS (stat "pfh_cap_lds")
 void range_image_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
                      const pfx_camera& cam, float4* d_points);
 int64_t narf_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
