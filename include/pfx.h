@@ -346,6 +346,22 @@ pfx_status pfx_narf_keypoints_dev(pfx_ctx* ctx, const float* d_x, const float* d
  * "border_traits" (uint32 bitset, PCL BorderTrait order), "range" (float).            */
 pfx_status pfx_narf_debug_image(pfx_ctx* ctx, const char* which, void* out, int64_t count);
 
+/* Test hook of the uniform grid (host buffers): builds the normal-radius grid of a cloud and
+ * copies it out.
+ *   mode 0:  exact build (bounds pass, radix sort); leaves the bounds hint of this grid
+ *   mode 1:  speculative build on that hint (counting sort where eligible), then what a caller
+ *            does: the validation word is read back and, when non-zero, the grid is rebuilt
+ *            exactly; the arrays are those of the grid the caller ends up with
+ *   mode -1: no build, the arrays of the grid the last call left (n must be its point count)
+ * Outputs, each nullable: perm[n], skeys[n], sp[4 n] (x, y, z, 0 per sorted position),
+ * cell_start[ncells + 2] (cell_start_cap: elements the buffer holds; too few ->
+ * PFX_ERR_CAPACITY), params[4] = the exact cell mapping (origin x, y, z, 1 / cell),
+ * info[8] = nx, ny, nz, ncells, the raw validation word of the (first) build, its builder
+ * (0 radix sort, 1 counting sort), 1 if it was rebuilt exactly, the counting builder's cell cap. */
+pfx_status pfx_grid_debug(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
+                          double radius, int32_t mode, int32_t* perm, uint32_t* skeys, float* sp,
+                          int32_t* cell_start, int64_t cell_start_cap, double* params, int64_t* info);
+
 /* ---- the reference's keypoint -> cloud mapping (keypoints.h:227-229) ----------------- */
 /* k_xyz[i] = cloud[idx[i]] for 0 <= idx[i] < n (the reference indexes the cloud with pixel
  * indices; out-of-range indices are an out-of-bounds read there and are skipped here).

@@ -121,6 +121,8 @@ _SIGS = {
     "pfx_narf_keypoints_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(Camera),
                                        ctypes.POINTER(NarfParams), c_vp, c_i64, c_i64p]),
     "pfx_narf_debug_image": (c_int, [c_vp, ctypes.c_char_p, c_vp, c_i64]),
+    "pfx_grid_debug": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_dbl, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_i64,
+                               c_vp, c_vp]),
     "pfx_gather_points_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp,
                                       c_i64, c_i64p]),
     "pfx_nearest_descriptors_dev": (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, ctypes.c_int32,
@@ -160,6 +162,9 @@ _SIGS = {
                                     ctypes.c_double, ctypes.c_int32, c_vp, c_i64p, c_vp]),
 }
 
+# test hooks an older library loaded through PFX_LIB (A/B runs against a previous build) may lack
+_TEST_HOOKS = {"pfx_grid_debug"}
+
 _lib = None
 
 
@@ -185,7 +190,11 @@ def lib():
             pass
         lb = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in _SIGS.items():
-            fn = getattr(lb, name)
+            fn = getattr(lb, name, None)
+            if fn is None:
+                if name in _TEST_HOOKS and os.environ.get("PFX_LIB"):
+                    continue
+                raise AttributeError(f"{LIB_PATH} does not export {name}")
             fn.restype = res
             fn.argtypes = args
         _lib = lb

@@ -213,6 +213,31 @@ class Context:
         self._check(self._lib.pfx_narf_debug_image(self.h, which.encode(), _ptr(out), out.size))
         return out.reshape(height, width)
 
+    def grid_debug(self, x, y, z, r, mode=0):
+        """Test hook (pfx_grid_debug): the normal-radius grid of a cloud, built exactly (mode 0, leaves
+        the bounds hint) or speculatively on that hint (mode 1, rebuilt exactly when its validation
+        word is non-zero, as the callers do).  Returns a dict of perm, skeys, sp, cell_start, the
+        exact cell mapping (ox, oy, oz, inv, nx, ny, nz, ncells), the raw validation `word`, the
+        `builder` of the first build ("sort" / "count"), `rerun` and the counting builder's `cap`."""
+        x, y, z = map(_f32, (x, y, z))
+        n = len(x)
+        info = np.zeros(8, dtype=np.int64)
+        params = np.zeros(4, dtype=np.float64)
+        self._check(self._lib.pfx_grid_debug(self.h, _ptr(x), _ptr(y), _ptr(z), n, float(r), int(mode), None, None,
+                                             None, None, 0, _ptr(params), _ptr(info)))
+        ncells = int(info[3])
+        perm = np.empty(n, dtype=np.int32)
+        skeys = np.empty(n, dtype=np.uint32)
+        sp = np.empty((n, 4), dtype=np.float32)
+        cell_start = np.empty(ncells + 2, dtype=np.int32)
+        self._check(self._lib.pfx_grid_debug(self.h, None, None, None, n, float(r), -1, _ptr(perm), _ptr(skeys),
+                                             _ptr(sp), _ptr(cell_start), cell_start.size, _ptr(params), _ptr(info)))
+        return {"perm": perm, "skeys": skeys, "sp": sp, "cell_start": cell_start,
+                "ox": float(params[0]), "oy": float(params[1]), "oz": float(params[2]), "inv": float(params[3]),
+                "nx": int(info[0]), "ny": int(info[1]), "nz": int(info[2]), "ncells": ncells,
+                "word": int(info[4]), "builder": "count" if info[5] else "sort", "rerun": bool(info[6]),
+                "cap": int(info[7])}
+
     # ---- device (torch tensor) entry points, stream-ordered on the ctx stream ---------
     def normals_dev(self, x, y, z, r, nx, ny, nz, curv, viewpoint=(0.0, 0.0, 0.0)):
         vp = _f32(viewpoint)

@@ -106,6 +106,9 @@ pfx_status pfx_ctx_create(int device, pfx_ctx** out) {
     PFX_HIP(hipSetDevice(device));
     ctx->on_own_stream = true;  // created on first use (check_ctx)
     ctx->stats["pfh_cap_lds"] = pfx::pfh_cap_lds();
+    // grid builds by builder (pfx_grid.hip), and speculative counting builds that met a fat cell
+    for (const char* s : {"grid_count_builds", "grid_sort_builds", "grid_hinted_sort_builds", "grid_fat_fallbacks"})
+      ctx->stats[s] = 0;
     *out = ctx;
     return PFX_OK;
   } catch (const Error& e) {
@@ -664,6 +667,62 @@ pfx_status pfx_narf_debug_image(pfx_ctx* ctx, const char* which, void* out, int6
   check_ctx(ctx);
   if (!which || !out) throw Error(PFX_ERR_INVALID, "narf_debug: null argument");
   pfx::narf_debug(ctx, which, out, count);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_grid_debug(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, double radius,
+                          int32_t mode, int32_t* perm, uint32_t* skeys, float* sp, int32_t* cell_start,
+                          int64_t cell_start_cap, double* params, int64_t* info) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  pfx::Grid& G = ctx->grid_a;
+  hipStream_t st = ctx->stream;
+  if (mode < -1 || mode > 1 || n < 0) throw Error(PFX_ERR_INVALID, "grid_debug: invalid arguments");
+  if (mode >= 0) {
+    if (n && (!x || !y || !z)) throw Error(PFX_ERR_INVALID, "grid_debug: null cloud");
+    float* dx = stage_in(ctx, "dbg_x", x, n);
+    float* dy = stage_in(ctx, "dbg_y", y, n);
+    float* dz = stage_in(ctx, "dbg_z", z, n);
+    pfx::build_grid(ctx, G, dx, dy, dz, n, radius, /*use_hint=*/mode == 1);
+    int word = 0;
+    const bool counted = G.counted;
+    bool rerun = false;
+    if (G.oob) {  // a caller's read of the validation word, and its exact rerun
+      int* h = ctx->readback<int>();
+      PFX_HIP(hipMemcpyAsync(h, G.oob, sizeof(int), hipMemcpyDeviceToHost, st));
+      PFX_HIP(hipStreamSynchronize(st));
+      word = *h;
+      G.oob = nullptr;
+      pfx::note_grid_word(ctx, G, word);
+      if (word != 0) {
+        pfx::build_grid(ctx, G, dx, dy, dz, n, radius);
+        rerun = true;
+      }
+    }
+    ctx->stats["grid_debug_word"] = word;
+    ctx->stats["grid_debug_builder"] = counted ? 1 : 0;
+    ctx->stats["grid_debug_rerun"] = rerun ? 1 : 0;
+  } else if (n != G.n) {
+    throw Error(PFX_ERR_INVALID, "grid_debug: the grid holds another point count");
+  }
+  const int64_t C = G.ncells;
+  if (cell_start && cell_start_cap < C + 2) throw Error(PFX_ERR_CAPACITY, "grid_debug: cell_start buffer too small");
+  if (perm && n) PFX_HIP(hipMemcpyAsync(perm, G.perm, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+  if (skeys && n) PFX_HIP(hipMemcpyAsync(skeys, G.skeys, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+  if (sp && n) PFX_HIP(hipMemcpyAsync(sp, G.sp, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, st));
+  if (cell_start)
+    PFX_HIP(hipMemcpyAsync(cell_start, G.cell_start, sizeof(int32_t) * (C + 2), hipMemcpyDeviceToHost, st));
+  PFX_HIP(hipStreamSynchronize(st));
+  if (params) {
+    params[0] = G.dox; params[1] = G.doy; params[2] = G.doz; params[3] = G.dinv;
+  }
+  if (info) {
+    info[0] = G.nx; info[1] = G.ny; info[2] = G.nz; info[3] = C;
+    info[4] = ctx->stats["grid_debug_word"];
+    info[5] = ctx->stats["grid_debug_builder"];
+    info[6] = ctx->stats["grid_debug_rerun"];
+    info[7] = pfx::kGridFatCap;
+  }
   PFX_API_END(ctx)
 }
 

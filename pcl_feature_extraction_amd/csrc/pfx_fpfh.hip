@@ -878,6 +878,7 @@ bool fpfh_validate_grid(pfx_ctx* ctx) {
   G.oob = nullptr;
   PFX_HIP(hipEventSynchronize(ctx->grid_b_oob_ev));
   if (*ctx->grid_b_hoob == 0) return false;
+  note_grid_word(ctx, G, *ctx->grid_b_hoob);
   ctx->stats["fpfh_speculative_reruns"] += 1;
   // exact rebuild (bounds readback; refreshes the hint); the preparation still describes it
   const float* x = ctx->prep_x;

@@ -10,6 +10,7 @@
 // Non-finite points get key C and sort behind every cell (never a neighbour, as PCL's
 // kd-tree skips them).
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -96,33 +97,194 @@ __global__ void __launch_bounds__(256) k_bbox_reduce(uint32_t* __restrict__ mm, 
   if (t < 6) mm[nblocks * 6 + t] = s[t][0];
 }
 
+__device__ __forceinline__ uint64_t lanemask_lt64() {
+  const int lane = threadIdx.x & 63;
+  return lane == 0 ? 0ull : (~0ull >> (64 - lane));
+}
+
+// the mapping point -> cell of both builders
+struct CellMap {
+  double inv, ox, oy, oz, hx, hy, hz;
+  int32_t nx, ny, nz;
+};
+
+// linear cell key of a point (C = nx * ny * nz for a non-finite one)
 // oob (nullable, speculative bounds): counts the finite points outside [lo, hi] (clamped keys
 // are then not a valid grid; the caller rebuilds on exact bounds)
-__global__ void __launch_bounds__(256) k_cell_keys(const float* __restrict__ x, const float* __restrict__ y,
-                                                   const float* __restrict__ z, int64_t n, double inv,
-                                                   double ox, double oy, double oz, int32_t nx, int32_t ny,
-                                                   int32_t nz, uint32_t* __restrict__ keys,
-                                                   uint32_t* __restrict__ vals, int* __restrict__ oob,
-                                                   double hx, double hy, double hz) {
-  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float px = x[i], py = y[i], pz = z[i];
-  uint32_t key = (uint32_t)((int64_t)nx * ny * nz);
+__device__ __forceinline__ uint32_t point_key(const CellMap& m, float px, float py, float pz,
+                                              int* __restrict__ oob) {
+  uint32_t key = (uint32_t)((int64_t)m.nx * m.ny * m.nz);
   if (isfinite(px) && isfinite(py) && isfinite(pz)) {
     // (exactly the points the clamp below would move: cell index outside [0, dims))
-    if (oob && ((double)px < ox || (double)py < oy || (double)pz < oz || (double)px > hx || (double)py > hy ||
-                (double)pz > hz))
+    if (oob && ((double)px < m.ox || (double)py < m.oy || (double)pz < m.oz || (double)px > m.hx ||
+                (double)py > m.hy || (double)pz > m.hz))
       atomicAdd(oob, 1);
-    int64_t ix = (int64_t)floor(((double)px - ox) * inv);
-    int64_t iy = (int64_t)floor(((double)py - oy) * inv);
-    int64_t iz = (int64_t)floor(((double)pz - oz) * inv);
-    ix = ix < 0 ? 0 : (ix >= nx ? nx - 1 : ix);
-    iy = iy < 0 ? 0 : (iy >= ny ? ny - 1 : iy);
-    iz = iz < 0 ? 0 : (iz >= nz ? nz - 1 : iz);
-    key = (uint32_t)((ix * ny + iy) * nz + iz);
+    int64_t ix = (int64_t)floor(((double)px - m.ox) * m.inv);
+    int64_t iy = (int64_t)floor(((double)py - m.oy) * m.inv);
+    int64_t iz = (int64_t)floor(((double)pz - m.oz) * m.inv);
+    ix = ix < 0 ? 0 : (ix >= m.nx ? m.nx - 1 : ix);
+    iy = iy < 0 ? 0 : (iy >= m.ny ? m.ny - 1 : iy);
+    iz = iz < 0 ? 0 : (iz >= m.nz ? m.nz - 1 : iz);
+    key = (uint32_t)((ix * m.ny + iy) * m.nz + iz);
   }
-  keys[i] = key;
+  return key;
+}
+
+__global__ void __launch_bounds__(256) k_cell_keys(const float* __restrict__ x, const float* __restrict__ y,
+                                                   const float* __restrict__ z, int64_t n, CellMap m,
+                                                   uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                   int* __restrict__ oob) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  keys[i] = point_key(m, x[i], y[i], z[i], oob);
   vals[i] = (uint32_t)i;
+}
+
+// ---- the counting-sort builder (speculative builds): the cell key is bounded, so one count per
+// cell, one scan and one scatter replace the radix sort, and the order inside a cell (ascending
+// caller index, the radix sort's stability) is restored cell by cell afterwards.
+// The counts live in cell_start: [0, C) the cells, [C] 0, [C + 1, C + 1 + blocks) the non-finite
+// points of each 256-point block of the cloud; one exclusive scan turns them into the cells'
+// first positions, the finite count at [C] and each block's first tail position.
+
+constexpr int kCountBlock = 256;
+constexpr int64_t kGridCountMaxPoints = int64_t(1) << 18;  // the default builder above this: radix sort
+// lanes of a wave with one key share one atomic, for the first keys of the wave (a scan-ordered
+// cloud has 1-3 keys per wave; a shuffled one ~64, whose lanes then count on their own)
+constexpr int kAggRounds = 4;
+
+__global__ void __launch_bounds__(256) k_count_zero(int32_t* __restrict__ p, int64_t m, int* __restrict__ oob) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x)
+    p[i] = 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *oob = 0;
+}
+
+// P1: key and arrival rank of every point.  A finite point's rank is the old value of its cell's
+// count (any order: k_count_order restores the index order); a non-finite one's is its rank among
+// the non-finite points of its block, in index order (so the tail needs no reordering).
+__global__ void __launch_bounds__(kCountBlock) k_count_keys(const float* __restrict__ x, const float* __restrict__ y,
+                                                            const float* __restrict__ z, int64_t n, CellMap m,
+                                                            uint32_t* __restrict__ keys, uint32_t* __restrict__ rank,
+                                                            int32_t* __restrict__ counts, int* __restrict__ oob) {
+  const int64_t i = blockIdx.x * (int64_t)kCountBlock + threadIdx.x;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t C = (uint32_t)((int64_t)m.nx * m.ny * m.nz);
+  const bool live = i < n;
+  uint32_t key = C;
+  if (live) key = point_key(m, x[i], y[i], z[i], oob);
+  const bool fin = live && key != C;
+  // (every lane stays in the wave-wide steps below)
+  uint64_t todo = __ballot(fin);
+  int leader = lane, offs = 0, cnt = 1;
+  for (int it = 0; it < kAggRounds && todo; ++it) {
+    const int l = __builtin_ctzll(todo);
+    const uint32_t k = (uint32_t)__shfl((int)key, l);
+    const uint64_t same = __ballot(fin && key == k);
+    if (fin && key == k) {
+      leader = l;
+      offs = __popcll(same & lanemask_lt64());
+      cnt = __popcll(same);
+    }
+    todo &= ~same;
+  }
+  int base = 0;
+  if (fin && lane == leader) base = atomicAdd(&counts[key], cnt);
+  base = __shfl(base, leader);
+  uint32_t r = (uint32_t)(base + offs);
+  // non-finite points: ballot prefix inside the block
+  __shared__ int s_nf[kCountBlock / 64];
+  const bool nf = live && !fin;
+  const uint64_t bm = __ballot(nf);
+  if (lane == 0) s_nf[wv] = __popcll(bm);
+  __syncthreads();
+  if (nf) {
+    int before = __popcll(bm & lanemask_lt64());
+    for (int w = 0; w < wv; ++w) before += s_nf[w];
+    r = (uint32_t)before;
+  }
+  if (threadIdx.x == 0) {
+    int total = 0;
+    for (int w = 0; w < kCountBlock / 64; ++w) total += s_nf[w];
+    counts[(int64_t)C + 1 + blockIdx.x] = total;
+  }
+  if (live) {
+    keys[i] = key;
+    rank[i] = r;
+  }
+}
+
+// P3: every point to slot (first position of its cell + arrival rank) of the scratch, packed
+// (x, y, z, caller index); the cell key of a slot is already final (one key per cell)
+__global__ void __launch_bounds__(kCountBlock) k_count_scatter(const float* __restrict__ x, const float* __restrict__ y,
+                                                               const float* __restrict__ z, int64_t n, uint32_t C,
+                                                               const uint32_t* __restrict__ keys,
+                                                               const uint32_t* __restrict__ rank,
+                                                               const int32_t* __restrict__ cell_start,
+                                                               float4* __restrict__ scr, uint32_t* __restrict__ skeys) {
+  const int64_t i = blockIdx.x * (int64_t)kCountBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t key = keys[i];
+  const int64_t at = key < C ? (int64_t)key : (int64_t)C + 1 + blockIdx.x;
+  const int64_t slot = (int64_t)cell_start[at] + rank[i];
+  scr[slot] = make_float4(x[i], y[i], z[i], __uint_as_float((uint32_t)i));
+  skeys[slot] = key;
+}
+
+// P4: the point of slot s goes to (first position of its cell + the number of smaller caller
+// indices in the cell); a cell above kGridFatCap points is left unordered and reported through
+// the validation word (the m^2 reads of a cell stay bounded), the non-finite tail is in order.
+// The caller indices of every cell that reaches into the workgroup's 256 slots are staged in LDS
+// first (at most a cap's worth on either side: a longer cell is fat and skipped), so the m reads
+// per point are LDS broadcasts (the same loop on global loads took 108 us per build in the step).
+constexpr int kOrderWin = 256 + 2 * kGridFatCap;
+__global__ void __launch_bounds__(256) k_count_order(const float4* __restrict__ scr, const uint32_t* __restrict__ skeys,
+                                                     int64_t n, uint32_t C, int32_t* __restrict__ cell_start,
+                                                     int32_t* __restrict__ perm, float* __restrict__ sx,
+                                                     float* __restrict__ sy, float* __restrict__ sz,
+                                                     float4* __restrict__ sp, int* __restrict__ oob) {
+  __shared__ uint32_t s_idx[kOrderWin];
+  __shared__ int64_t s_win[2];
+  const int64_t s0 = blockIdx.x * (int64_t)256, s = s0 + threadIdx.x;
+  if (s == 0) cell_start[(int64_t)C + 1] = (int32_t)n;  // (held block 0's tail position until here)
+  if (threadIdx.x == 0) {
+    const int64_t last = s0 + 255 < n ? s0 + 255 : n - 1;
+    const uint32_t k0 = skeys[s0], k1 = skeys[last];
+    int64_t w0 = s0, w1 = s0;  // (a workgroup of tail slots stages nothing)
+    if (k0 < C) {
+      w0 = cell_start[k0];
+      w1 = cell_start[(k1 < C ? k1 : C - 1) + 1];
+      w0 = w0 > s0 - kGridFatCap ? w0 : s0 - kGridFatCap;
+      w1 = w1 < s0 + 256 + kGridFatCap ? w1 : s0 + 256 + kGridFatCap;
+    }
+    s_win[0] = w0;
+    s_win[1] = w1;
+  }
+  __syncthreads();
+  const int64_t w0 = s_win[0], w1 = s_win[1];
+  for (int64_t t = w0 + threadIdx.x; t < w1; t += 256) s_idx[t - w0] = __float_as_uint(scr[t].w);
+  __syncthreads();
+  if (s >= n) return;
+  const uint32_t key = skeys[s];
+  const float4 v = scr[s];
+  const uint32_t idx = __float_as_uint(v.w);
+  int64_t d = s;
+  if (key < C) {
+    const int32_t start = cell_start[key], end = cell_start[key + 1];
+    if (end - start > kGridFatCap) {
+      if (s == start) atomicOr(oob, kGridFatBit);
+      return;
+    }
+    const uint32_t* cell = s_idx + (start - w0);
+    const int m = end - start;
+    int before = 0;
+    for (int t = 0; t < m; ++t) before += cell[t] < idx ? 1 : 0;
+    d = (int64_t)start + before;
+  }
+  perm[d] = (int32_t)idx;
+  sx[d] = v.x;
+  sy[d] = v.y;
+  sz[d] = v.z;
+  sp[d] = make_float4(v.x, v.y, v.z, 0.0f);
 }
 
 // cell_start[0, m) = v: a plain kernel launch (hipMemsetD32Async spent ~70 us of host time per
@@ -154,6 +316,13 @@ __global__ void __launch_bounds__(256) k_gather_sorted(const float* __restrict__
   sy[i] = b;
   sz[i] = c;
   sp[i] = make_float4(a, b, c, 0.0f);
+}
+
+// exact builds: does any cell hold more than kGridFatCap points?  (flag zeroed by the build)
+__global__ void __launch_bounds__(256) k_fat_cells(const int32_t* __restrict__ cell_start, int64_t ncells,
+                                                   int* __restrict__ flag) {
+  const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (c < ncells && cell_start[c + 1] - cell_start[c] > kGridFatCap) *flag = 1;
 }
 
 }  // namespace
@@ -207,6 +376,7 @@ void build_grid(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const
   g.ux = d_x; g.uy = d_y; g.uz = d_z;
   double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
   g.oob = nullptr;
+  g.hint_user |= use_hint;
   if (use_hint && g.have_hint && n > 0) {
     // speculative: the previous exact bounds, widened (no bounds pass, no host round trip)
     for (int d = 0; d < 3; ++d) {
@@ -244,6 +414,62 @@ void build_grid(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const
   g.inv = (float)inv;
   const int64_t C = g.ncells;
 
+  const CellMap cm{inv, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], g.nx, g.ny, g.nz};
+  g.dinv = inv;
+  g.dox = lo[0]; g.doy = lo[1]; g.doz = lo[2];
+  g.perm = g.b_perm.as<int32_t>(n + 1);
+  g.sx = g.b_sx.as<float>(n + 1);
+  g.sy = g.b_sy.as<float>(n + 1);
+  g.sz = g.b_sz.as<float>(n + 1);
+  g.sp = g.b_sp.as<float4>(n + 1);
+  uint32_t* keys = g.b_keys.as<uint32_t>(n + 1);
+  uint32_t* keys2 = g.b_keys2.as<uint32_t>(n + 1);
+  uint32_t* vals = g.b_vals.as<uint32_t>(n + 1);
+  g.skeys = keys2;  // cell key per sorted position
+
+  // Speculative builds of small clouds take the counting-sort builder, unless this grid has shown
+  // a fat cell: 6 launches instead of 16 where the build is launch-bound (configs[1], 100k
+  // points).  Its per-point atomics run at the chip-wide atomic rate (k_count_keys: 77 us per 1M
+  // points, ~13 G atomics/s) and slow the kernels of the other stream meanwhile (headline, 1M
+  // points: 203-205 against 209-212 Mpoints/s with the radix sort), so larger clouds keep the
+  // radix sort.  PFX_GRID_BUILD=sort|count forces either builder at any size (A/B runs).  Exact
+  // builds always use the radix sort: their callers have no validation word to read, and the
+  // counting builder may leave a fat cell unordered.
+  if (g.oob && g.fat_pending) {  // the last exact build's finding (normally long complete)
+    PFX_HIP(hipEventSynchronize(g.fat_ev));
+    g.fat_pending = false;
+    g.fat = *g.h_fat != 0;
+  }
+  const char* mode = std::getenv("PFX_GRID_BUILD");
+  const bool want_count = mode && std::strcmp(mode, "count") == 0
+                              ? true
+                              : (mode && std::strcmp(mode, "sort") == 0 ? false : n <= kGridCountMaxPoints);
+  g.counted = g.oob != nullptr && n > 0 && want_count && !g.fat;
+  ++ctx->stats[g.counted ? "grid_count_builds" : "grid_sort_builds"];
+  if (g.oob && !g.counted) ++ctx->stats["grid_hinted_sort_builds"];
+  if (g.counted) {
+    const int64_t blocks = ceil_div(n, kCountBlock);
+    const int64_t m = C + 1 + blocks;  // cell counts, [C] = 0, per-block non-finite counts
+    size_t scan_bytes = 0;
+    PFX_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (int32_t*)nullptr, (int32_t*)nullptr, int32_t(0), (size_t)m,
+                                    rocprim::plus<int32_t>(), st));
+    void* tmp = g.b_tmp.get(scan_bytes + 16);
+    g.cell_start = g.b_start.as<int32_t>(m + 1);
+    float4* scr = g.b_scr.as<float4>(n + 1);
+    TimeScope ts(ctx, "grid_build");
+    k_count_zero<<<(unsigned)std::min<int64_t>(ceil_div(m, 256), 2048), 256, 0, st>>>(g.cell_start, m, g.oob);
+    k_count_keys<<<(unsigned)blocks, kCountBlock, 0, st>>>(d_x, d_y, d_z, n, cm, keys, vals, g.cell_start, g.oob);
+    check_launch("k_count_keys");
+    PFX_HIP(rocprim::exclusive_scan(tmp, scan_bytes, g.cell_start, g.cell_start, int32_t(0), (size_t)m,
+                                    rocprim::plus<int32_t>(), st));
+    k_count_scatter<<<(unsigned)blocks, kCountBlock, 0, st>>>(d_x, d_y, d_z, n, (uint32_t)C, keys, vals, g.cell_start,
+                                                              scr, keys2);
+    k_count_order<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(scr, keys2, n, (uint32_t)C, g.cell_start, g.perm, g.sx,
+                                                              g.sy, g.sz, g.sp, g.oob);
+    check_launch("k_count_order");
+    return;
+  }
+
   // onesweep radix sort even at ~1M keys: the default config switches to merge sort below 2^20
   // items (30+ block-merge launches, ~0.4 ms at 1M points on gfx950)
   using SortCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
@@ -258,18 +484,7 @@ void build_grid(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const
   auto rev = rocprim::make_reverse_iterator(static_cast<int32_t*>(nullptr));
   PFX_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, rev, rev, (size_t)(C + 1), rocprim::minimum<int32_t>(), st));
   void* tmp = g.b_tmp.get(std::max(sort_bytes, scan_bytes) + 16);
-  uint32_t* keys = g.b_keys.as<uint32_t>(n + 1);
-  uint32_t* keys2 = g.b_keys2.as<uint32_t>(n + 1);
-  uint32_t* vals = g.b_vals.as<uint32_t>(n + 1);
-  g.perm = g.b_perm.as<int32_t>(n + 1);
-  g.skeys = keys2;  // radix-sort output: cell key per sorted position
-  g.sx = g.b_sx.as<float>(n + 1);
-  g.sy = g.b_sy.as<float>(n + 1);
-  g.sz = g.b_sz.as<float>(n + 1);
-  g.sp = g.b_sp.as<float4>(n + 1);
   g.cell_start = g.b_start.as<int32_t>(C + 2);
-  g.dinv = inv;
-  g.dox = lo[0]; g.doy = lo[1]; g.doz = lo[2];
   {
     TimeScope ts(ctx, "grid_build");
     // cell_start[c] = first sorted position with key >= c: mark the first position of every
@@ -278,9 +493,7 @@ void build_grid(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const
                                                                                        (int32_t)n);
     if (g.oob) k_fill_i32<<<1, 64, 0, st>>>(g.oob, 1, 0);
     if (n > 0) {
-      k_cell_keys<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(d_x, d_y, d_z, n, inv, lo[0], lo[1], lo[2],
-                                                              g.nx, g.ny, g.nz, keys, vals, g.oob, hi[0], hi[1],
-                                                              hi[2]);
+      k_cell_keys<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(d_x, d_y, d_z, n, cm, keys, vals, g.oob);
       check_launch("k_cell_keys");
       PFX_HIP(rocprim::radix_sort_pairs<SortCfg>(tmp, sort_bytes, keys, keys2, vals,
                                         reinterpret_cast<uint32_t*>(g.perm), (size_t)n, 0, bits, st));
@@ -291,6 +504,20 @@ void build_grid(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const
           d_x, d_y, d_z, n, reinterpret_cast<uint32_t*>(g.perm), g.sx, g.sy, g.sz, g.sp);
       check_launch("k_gather_sorted");
     }
+  }
+  if (!g.oob && n > 0 && g.hint_user) {
+    // an exact build says whether the counting builder could order this cloud's cells; the next
+    // hinted build of this grid reads the answer
+    int* d_fat = g.b_fat.as<int>(1);
+    if (!g.h_fat) PFX_HIP(hipHostMalloc((void**)&g.h_fat, 64, hipHostMallocDefault));
+    if (!g.fat_ev) PFX_HIP(hipEventCreateWithFlags(&g.fat_ev, hipEventDisableTiming));
+    if (g.fat_pending) PFX_HIP(hipEventSynchronize(g.fat_ev));  // (an unread earlier answer: superseded)
+    k_fill_i32<<<1, 64, 0, st>>>(d_fat, 1, 0);
+    k_fat_cells<<<(unsigned)ceil_div(C, 256), 256, 0, st>>>(g.cell_start, C, d_fat);
+    check_launch("k_fat_cells");
+    PFX_HIP(hipMemcpyAsync(g.h_fat, d_fat, sizeof(int), hipMemcpyDeviceToHost, st));
+    PFX_HIP(hipEventRecord(g.fat_ev, st));
+    g.fat_pending = true;
   }
 }
 

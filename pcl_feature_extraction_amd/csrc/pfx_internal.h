@@ -77,22 +77,43 @@ struct Grid {
   int32_t* perm = nullptr;                            // sorted position -> caller index
   int32_t* cell_start = nullptr;                      // ncells + 1 prefix (by linear cell key)
   const uint32_t* skeys = nullptr;                    // cell key of each sorted position
-  DevBuf b_sx, b_sy, b_sz, b_sp, b_perm, b_start, b_keys, b_keys2, b_vals, b_tmp, b_minmax, b_oob;
+  DevBuf b_sx, b_sy, b_sz, b_sp, b_perm, b_start, b_keys, b_keys2, b_vals, b_tmp, b_minmax, b_oob, b_scr, b_fat;
   // Speculative bounds (build_grid with use_hint): the last exact bounds of this grid, widened;
   // when a build uses them, `oob` (device int) counts the finite points outside, and the grid is
   // valid only if it stays 0 -- the caller checks it at its next readback and rebuilds exactly
   bool have_hint = false;
   double hint_lo[3] = {0, 0, 0}, hint_hi[3] = {0, 0, 0};
   int* oob = nullptr;  // non-null iff the current build is speculative
+  // A speculative build by the counting-sort builder leaves a cell above kGridFatCap points
+  // unordered and sets kGridFatBit in the same word (so every `oob != 0` test covers it).  Where
+  // the host reads the word it notes the bit here (note_grid_word): later hinted builds of this
+  // grid use the radix builder.  Every exact build states afresh whether its cloud has such a cell
+  // (one word copied to pinned memory in stream order, read by the next hinted build, long
+  // complete by then), so a cloud known to be fat never takes the counting builder at all.
+  mutable bool fat = false;
+  int* h_fat = nullptr;  // pinned
+  hipEvent_t fat_ev = nullptr;
+  bool fat_pending = false;
+  bool hint_user = false;  // some caller builds this grid speculatively (only then is the answer wanted)
+  bool counted = false;  // the current build came from the counting-sort builder
   uint64_t gen = 0;    // incremented by every build (consumers holding a grid check it)
   void release() {
     b_sx.release(); b_sy.release(); b_sz.release(); b_sp.release(); b_perm.release(); b_start.release();
     b_keys.release(); b_keys2.release(); b_vals.release(); b_tmp.release(); b_minmax.release(); b_oob.release();
+    b_scr.release(); b_fat.release();
+    if (fat_ev) { (void)hipEventSynchronize(fat_ev); (void)hipEventDestroy(fat_ev); fat_ev = nullptr; }
+    if (h_fat) { (void)hipHostFree(h_fat); h_fat = nullptr; }
+    fat_pending = false;
     have_hint = false;
+    fat = false;
     oob = nullptr;
     ++gen;
   }
 };
+
+// the counting-sort builder's cell cap and its bit in a speculative build's validation word
+constexpr int kGridFatCap = 1024;
+constexpr int kGridFatBit = 1 << 30;
 
 // Per-query view of a grid handed to kernels by value.
 struct GridView {
@@ -244,6 +265,12 @@ void build_grid(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const
 // bounding box of the finite points (0 when there are none), synchronous
 void points_bbox(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const float* d_z, int64_t n,
                  double lo[3], double hi[3]);
+// the host's read of a speculative build's validation word: a fat cell is remembered on the grid
+inline void note_grid_word(pfx_ctx* ctx, const Grid& g, int word) {
+  if (!(word & kGridFatBit)) return;
+  g.fat = true;
+  ++ctx->stats["grid_fat_fallbacks"];
+}
 inline GridView view(const Grid& g) {
   GridView v;
   v.sx = g.sx; v.sy = g.sy; v.sz = g.sz; v.sp = g.sp; v.perm = g.perm; v.cell_start = g.cell_start;

@@ -58,7 +58,7 @@ constexpr int kCapHuge = 1 << 18, kBucketsHuge = 4096, kHugeBlocks = PFX_HUGE_BL
 constexpr int kNtQuery = PFX_NT_QUERY, kNtMid8 = PFX_NT_MID8, kNtMid = PFX_NT_MID, kNtHuge = 256;
 
 // The control block of a list build (device ints, zeroed by k_list_init, read back whole).
-// The tile counts come first: k_tile_class writes them once per build, so they survive a retry of
+// The tile counts come first: k_tile_class (or k_tile_cells) writes them once per build, so they survive a retry of
 // the list kernels (the set-up is not repeated); everything from kRetryFirst on is written by the
 // list kernels and zeroed again before each retry.
 enum Counter : int {
@@ -110,7 +110,7 @@ __device__ __forceinline__ int query_tier(int k) {
   return k <= kCapQuery ? 0 : (k <= kCapMid8 ? 1 : (k <= kCapMid ? 2 : 3));
 }
 
-// Tile record (written by k_tile_class, one per tile, in class order): the 9 candidate runs of
+// Tile record (written by k_tile_class or k_tile_cells, one per tile, in class order): the 9 candidate runs of
 // the tile's 3x3x3 block, its first query (index into qpos) and query count.  A workgroup loads
 // the record of its next tile one lane per word while it works on the current one and unpacks it
 // with readlane into SGPRs, so a tile starts with no dependent global loads (the old chain
@@ -278,6 +278,106 @@ __global__ void __launch_bounds__(256) k_tile_class(GridView g, const int32_t* _
       const int64_t at = c == 3 ? slot : (c == 0 ? n + slot : (c == 1 ? 2 * n - 1 - slot : n - 1 - slot));
       rec_write(recs + at * kRecInts, R, start, qn);
       if (c == 2) wide[slot] = (int32_t)at;
+    }
+  }
+}
+
+// Unmasked builds: the queries are the finite points in cell order, so the tiles are the 16-query
+// chunks of each cell and cell_start states them outright.  A thread takes kCellsPerThread
+// consecutive cells: block_runs and the class once per cell (k_tile_class: once per tile), the
+// workgroup's tiles per class summed in LDS and reserved with one atomic per class and workgroup
+// (one per wave and class made ~15,000 same-address atomics on the 1M-point room, whose occupied
+// cells are spread thinly over 3M: 229 us), then each cell's ceil(m / 16) records, in the same
+// regions.  Slots follow the cells inside a workgroup, so the records stay roughly in cell order
+// as before.  A cell above kCoopTiles tiles is written by the whole wave, so no lane is left
+// alone with a very full cell.
+constexpr int kCoopTiles = 16;
+constexpr int kCellsPerThread = 8;
+constexpr int64_t kCellsMinGrid = int64_t(256) * 256 * kCellsPerThread;  // cells that give every CU a workgroup
+__device__ __forceinline__ int tile_class(int T) {
+  // 3: small tiles (<= kTcapSmall candidates), 0: sparse, 1: dense, 2: wide (as k_tile_class)
+  return T <= kTcapSmall ? 3 : (T <= kTcapSparse ? 0 : (T <= kTcapDense ? 1 : 2));
+}
+__global__ void __launch_bounds__(256) k_tile_cells(GridView g, int64_t ncells, int32_t* __restrict__ recs, int64_t n,
+                                                    int32_t* __restrict__ wide, int* __restrict__ counts) {
+  __shared__ int s_wave[4][4];  // [class][wave] tiles
+  __shared__ int s_base[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t c0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) * kCellsPerThread;
+  int32_t st[kCellsPerThread + 1];
+#pragma unroll
+  for (int j = 0; j <= kCellsPerThread; ++j) st[j] = g.cell_start[c0 + j <= ncells ? c0 + j : ncells];
+  // pass 1: tiles per class of this thread's cells
+  int cnt[4] = {0, 0, 0, 0};
+  unsigned cls_bits = 0;
+#pragma unroll
+  for (int j = 0; j < kCellsPerThread; ++j) {
+    const int m = st[j + 1] - st[j];
+    if (m > 0) {  // (cells past the grid's end repeat cell_start[ncells]: empty)
+      Runs R;
+      const int cls = tile_class(block_runs(g, (uint32_t)(c0 + j), R));
+      cls_bits |= (unsigned)cls << (2 * j);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) cnt[k] += cls == k ? (m + kQ - 1) / kQ : 0;
+    }
+  }
+  int first[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int incl = wave_incl_scan(cnt[k]);
+    first[k] = incl - cnt[k];
+    if (lane == 63) s_wave[k][wv] = incl;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int k = threadIdx.x;
+    const int total = s_wave[k][0] + s_wave[k][1] + s_wave[k][2] + s_wave[k][3];
+    const int ci = k == 3 ? kTilesSmall : (k == 2 ? kTilesWide : (k == 1 ? kTilesDense : kTilesSparse));
+    s_base[k] = total ? atomicAdd(&counts[ci], total) : 0;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    first[k] += s_base[k];
+    for (int w = 0; w < wv; ++w) first[k] += s_wave[k][w];
+  }
+  // pass 2: the records (every lane of the wave stays in the loop)
+  auto emit = [&](const Runs& Rc, int k, int slot, int32_t q0, int qn) {
+    // small at [0, n) upward, wide at [0, n) downward from n - 1
+    const int64_t at = k == 3 ? slot : (k == 0 ? n + slot : (k == 1 ? 2 * n - 1 - slot : n - 1 - slot));
+    rec_write(recs + at * kRecInts, Rc, q0, qn);
+    if (k == 2) wide[slot] = (int32_t)at;
+  };
+#pragma unroll  // (st[] stays in registers)
+  for (int j = 0; j < kCellsPerThread; ++j) {
+    const int32_t s = st[j], m = st[j + 1] - st[j];
+    const int nt = (m + kQ - 1) / kQ, cls = (int)((cls_bits >> (2 * j)) & 3u);
+    Runs R;
+#pragma unroll
+    for (int r = 0; r < 9; ++r) R.start[r] = 0;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) R.pref[r] = 0;
+    int slot = 0;
+    if (m > 0) {
+      block_runs(g, (uint32_t)(c0 + j), R);
+      slot = cls == 3 ? first[3] : (cls == 2 ? first[2] : (cls == 1 ? first[1] : first[0]));
+#pragma unroll
+      for (int k = 0; k < 4; ++k) first[k] += cls == k ? nt : 0;
+      if (nt <= kCoopTiles)
+        for (int i = 0; i < nt; ++i) emit(R, cls, slot + i, s + kQ * i, min(kQ, m - kQ * i));
+    }
+    uint64_t big = __ballot(m > 0 && nt > kCoopTiles);
+    while (big) {
+      const int l = __builtin_ctzll(big);
+      big &= big - 1;
+      Runs Rl;
+#pragma unroll
+      for (int r = 0; r < 9; ++r) Rl.start[r] = __shfl(R.start[r], l);
+#pragma unroll
+      for (int r = 0; r < 10; ++r) Rl.pref[r] = __shfl(R.pref[r], l);
+      const int32_t sl = __shfl(s, l), ml = __shfl(m, l);
+      const int fl = __shfl(slot, l), ntl = __shfl(nt, l), kl = __shfl(cls, l);
+      for (int i = lane; i < ntl; i += 64) emit(Rl, kl, fl + i, sl + kQ * i, min(kQ, ml - kQ * i));
     }
   }
 }
@@ -1580,6 +1680,7 @@ void publish(pfx_ctx* ctx, const char* tag, const ListsRb& rb, size_t list_words
   out.long_nq = (int64_t)rb.cur[3];
   out.slots = (int64_t)rb.cur[0];
   auto stat = [&](const char* what) -> int64_t& { return ctx->stats[std::string(tag) + what]; };
+  stat("_tiles_small") = rb.cnt[kTilesSmall];
   stat("_tiles_sparse") = rb.cnt[kTilesSparse];
   stat("_tiles_dense") = rb.cnt[kTilesDense];
   stat("_wide") = rb.cnt[kTilesWide];
@@ -1744,6 +1845,23 @@ struct ListBuild {
       // every finite point, in cell order: sorted positions [0, cell_start[ncells])
       k_list_init<<<nb, 256, 0, st>>>(qpos, n, G.cell_start + G.ncells, d_nq, counters, kNCounters, cursor, tq,
                                       tq_dev);
+      // tiles from the cells: one launch over the cells instead of the five over the queries
+      // below.  By default only where that launch fills the chip and the grid is not mostly empty
+      // cells: at least 256 CUs x 2048 cells per workgroup, at most 4 cells per point (1M-point
+      // room, 3M cells: 212.9 against 210.5 Mpoints/s mean of five; configs[1], 170k cells in 83
+      // workgroups: 47.6 against 48.1).  PFX_LIST_SETUP=scan|cells forces either (A/B runs, tests).
+      const char* mode = std::getenv("PFX_LIST_SETUP");
+      const bool cells = mode && std::strcmp(mode, "cells") == 0
+                             ? true
+                             : (mode && std::strcmp(mode, "scan") == 0
+                                    ? false
+                                    : G.ncells >= kCellsMinGrid && G.ncells <= std::max<int64_t>(4 * n, kCellsMinGrid));
+      ++ctx->stats[std::string(tag) + (cells ? "_setup_cells" : "_setup_scan")];
+      if (cells) {
+        k_tile_cells<<<(unsigned)ceil_div(G.ncells, 256 * kCellsPerThread), 256, 0, st>>>(g, G.ncells, recs, n, wq, counters);
+        check_launch("nblist cell tiles");
+        return;
+      }
     }
     k_seg_marks<<<nb, 256, 0, st>>>(qpos, G.skeys, d_nq, seg);
     PFX_HIP(rocprim::inclusive_scan(tmp, t2, seg, seg, (size_t)n, rocprim::maximum<int32_t>(), st));
@@ -1899,6 +2017,7 @@ struct ListBuild {
 bool build_lists_check(pfx_ctx* ctx, const Grid& G, NbLists& out, const char* tag) {
   auto B = [&](const char* what) -> DevBuf& { return ctx->bufs[bname(tag, what)]; };
   const ListsRb* rb = read_back(ctx, B("counters").ptr, B("cursor").ptr, B("nq").ptr, G.oob);
+  note_grid_word(ctx, G, rb->oob);
   const size_t words = B("list").bytes / sizeof(uint32_t);
   const int ran = (int)ctx->stats[std::string(tag) + "_ran_mid_tiers"];
   const int lacking = lists_lack(rb->cnt, rb->cur[0], words, B("scratch").ptr != nullptr, ran, rb->oob);
