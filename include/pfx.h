@@ -91,7 +91,20 @@ typedef struct pfx_narf_params {
   int32_t calculate_sparse_interest_image;
   int32_t no_of_polynomial_approximations_per_point; /* 0 (only 0 supported) */
   int32_t add_points_on_straight_edges;          /* 0 (only 0 supported)    */
-  /* RangeImageBorderExtractor::Parameters */
+  /* RangeImageBorderExtractor::Parameters.  Bounds (PFX_ERR_INVALID beyond them, before anything
+   * is launched): pixel_radius_plane_extraction in [0, 4] (at most 4 x 4 neighbours per pixel in the
+   * kernel's 25 sorted slots); the other three radii in [0, 1024].  Those three size no array, tile
+   * or mask in any kernel -- they are loop bounds, linear (borders, principal curvature) or
+   * quadratic (border direction) in run time per pixel -- and 1024 is the widest image accepted.
+   * support_size has no fixed upper bound: region-grow windows that outgrow the 128 x 128 masks or
+   * the 65,536-pixel bitmap move to the next tier, the last of which holds the whole image.  The
+   * two queue-based tiers keep at most 2048 pending pixels, which is one breadth-first level of the
+   * region plus the 64-pixel batch in flight.  A level of a filled region is a square ring clipped
+   * to the image: at most 8 d pixels at ring radius d and fewer than 4 min(width, height), so
+   * 1912 at 640 x 480 and 4 x 119 at 161 x 119 (tests run support 0.1 .. 1.0 there).  A region
+   * whose level outgrows the queue -- a whole-image region of a near-square image beyond ~500 px a
+   * side, or a contrived many-armed one -- ends the call with PFX_ERR_CAPACITY ("interest
+   * region-grow queue overflow"): a checked condition, never a wrong image. */
   int32_t pixel_radius_borders;                  /* 3   */
   int32_t pixel_radius_plane_extraction;         /* 2   */
   int32_t pixel_radius_border_direction;         /* 2   */
@@ -99,7 +112,9 @@ typedef struct pfx_narf_params {
   int32_t pixel_radius_principal_curvature;      /* 2   */
 } pfx_narf_params;
 
-/* RangeImagePlanar::createFromPointCloudWithFixedSize arguments */
+/* RangeImagePlanar::createFromPointCloudWithFixedSize arguments.  pfx_narf_keypoints* accepts
+ * width <= 1024 and width*height <= 307,200 (PFX_ERR_INVALID beyond); noise_level != 0 is
+ * PFX_ERR_UNSUPPORTED. */
 typedef struct pfx_camera {
   int32_t width, height;          /* 640, 480 (keypoints.h:204)     */
   float center_x, center_y;       /* 320, 240 (keypoints.h:205)     */
@@ -343,7 +358,9 @@ pfx_status pfx_narf_keypoints_dev(pfx_ctx* ctx, const float* d_x, const float* d
                                   int64_t* n_out);
 /* Debug/parity access to the NARF intermediates of the last pfx_narf_keypoints* call
  * (host buffers of width*height elements):  "interest" (float), "surface_change" (float),
- * "border_traits" (uint32 bitset, PCL BorderTrait order), "range" (float).            */
+ * "border_traits" (uint32 bitset, PCL BorderTrait order), "range" (float).  count must be exactly
+ * width*height of that call's camera: any other count is PFX_ERR_CAPACITY and nothing is written.
+ * A NARF call that fails leaves no images behind (PFX_ERR_INVALID until the next one succeeds). */
 pfx_status pfx_narf_debug_image(pfx_ctx* ctx, const char* which, void* out, int64_t count);
 
 /* Test hook of the uniform grid (host buffers): builds the normal-radius grid of a cloud and

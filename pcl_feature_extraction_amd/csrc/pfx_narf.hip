@@ -1298,20 +1298,32 @@ void range_image_dev(pfx_ctx* ctx, const float* x, const float* y, const float* 
 
 int64_t narf_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, const pfx_camera& cam,
                  const pfx_narf_params& p, std::vector<int32_t>& out) {
+  // the debug images belong to the last call, and only if it completed: a call that fails leaves
+  // none behind (narf_debug must never pair a new size with the buffers of an older run)
+  NarfState& S = state(ctx);
+  S.have_debug = false;
   PFX_CHECK(p.support_size > 0.0f, "narf: support_size must be > 0");
   if (p.no_of_polynomial_approximations_per_point != 0 || p.add_points_on_straight_edges != 0)
     throw Error(PFX_ERR_UNSUPPORTED, "narf: polynomial refinement / straight-edge points not supported");
   PFX_CHECK(p.pixel_radius_plane_extraction >= 0 && p.pixel_radius_plane_extraction <= 4,
             "narf: pixel_radius_plane_extraction must be in [0, 4]");
-  NarfState& S = state(ctx);
+  // the other three radii size no array, tile or mask (k_surface_change's beam[9] is the 3 x 3 ring
+  // of one step, whatever the radius); they are loop bounds, so the limit is on run time: 1024 is
+  // the widest image accepted below, and `d <= radius` must not run towards INT_MAX on a device
+  const int kMaxPixelRadius = 1024;
+  PFX_CHECK(p.pixel_radius_borders >= 0 && p.pixel_radius_borders <= kMaxPixelRadius &&
+                p.pixel_radius_border_direction >= 0 && p.pixel_radius_border_direction <= kMaxPixelRadius &&
+                p.pixel_radius_principal_curvature >= 0 && p.pixel_radius_principal_curvature <= kMaxPixelRadius,
+            "narf: pixel_radius_borders / _border_direction / _principal_curvature must be in [0, 1024]");
   hipStream_t st = ctx->stream;
   // the whole keypoint call on its stream (host round trips included): a stage timer
   TimeScope total(ctx, "narf", true);
   Img I = make_img(cam);
+  PFX_CHECK(I.w > 0 && I.h > 0 && (int64_t)I.w * I.h <= kFullWords * 32 && I.w <= 1024,
+            "narf: image larger than 640x480 pixels is not supported");
+  const int npx = I.w * I.h;
   S.w = I.w;
   S.h = I.h;
-  const int npx = I.w * I.h;
-  PFX_CHECK(npx <= kFullWords * 32 && I.w <= 1024, "narf: image larger than 640x480 pixels is not supported");
   float4* P = S.pts.as<float4>(npx);
   range_image_dev(ctx, x, y, z, n, cam, P);
   float4* surf = S.surf.as<float4>(npx);
@@ -1515,7 +1527,9 @@ void narf_debug(pfx_ctx* ctx, const std::string& which, void* out, int64_t count
   if (!ctx->narf || !ctx->narf->have_debug) throw Error(PFX_ERR_INVALID, "narf_debug: no NARF run yet");
   NarfState& S = *ctx->narf;
   const int64_t npx = (int64_t)S.w * S.h;
-  if (count < npx) throw Error(PFX_ERR_CAPACITY, "narf_debug: buffer smaller than width*height");
+  // exactly the last run's image: a larger buffer (another camera's size) would be handed back
+  // part filled, which reads as a stale image
+  if (count != npx) throw Error(PFX_ERR_CAPACITY, "narf_debug: count is not width*height of the last NARF run");
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   if (which == "interest") {
     PFX_HIP(hipMemcpy(out, S.interest.ptr, sizeof(float) * npx, hipMemcpyDeviceToHost));

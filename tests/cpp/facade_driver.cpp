@@ -12,6 +12,10 @@
 //   features.h:282-297 (filterCorrespondences) -> filtered.i32, transformation.f32; and the
 //   Harris3D / Harris6D branches (keypoints.h:150-176 + getKeypointsCloud keypoints.h:365-395)
 //   -> harris{3,6}d_xyz.f32 (snapped cloud points), harris{3,6}d_corners.f32 (x, y, z, intensity).
+// The PCD's VIEWPOINT becomes sensor_origin_ / sensor_orientation_ and, from them, the NARF sensor
+// pose (keypoints.h:207-216):
+//   facade_driver --pose <cloud.pcd>            prints that pose's 16 floats as hex bit patterns (no device)
+//   facade_driver --narf <cloud.pcd> <out_dir>  the NARF branch alone -> keypoints.i32
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -35,6 +39,12 @@ static bool read_pcd(const char* path, PointCloudRGB& c) {
     std::string key;
     ss >> key;
     if (key == "POINTS") ss >> n;
+    if (key == "VIEWPOINT") {  // tx ty tz qw qx qy qz, as pcl::PCDReader::readHeader fills them in
+      float v[7] = {0, 0, 0, 1, 0, 0, 0};
+      for (int i = 0; i < 7; ++i) ss >> v[i];
+      c.sensor_origin_ = Eigen::Vector4f(v[0], v[1], v[2], 0.0f);
+      c.sensor_orientation_ = Eigen::Quaternionf(v[3], v[4], v[5], v[6]);
+    }
     if (key == "DATA") {
       std::string kind;
       ss >> kind;
@@ -147,15 +157,19 @@ static void features_compute(typename Feature<PointRGB, FeatureType>::Ptr featur
   feature_extractor->compute(*descriptors);
 }
 
+// keypoints.h:207-216: the sensor pose from the cloud's PCD VIEWPOINT
+static Eigen::Affine3f sensor_pose_of(const PointCloudRGB& cloud) {
+  return Eigen::Affine3f(Eigen::Translation3f(cloud.sensor_origin_[0], cloud.sensor_origin_[1],
+                                              cloud.sensor_origin_[2])) *
+         Eigen::Affine3f(cloud.sensor_orientation_);
+}
+
 // keypoints.h:199-231 (NARF branch) -> the keypoint cloud (and the raw pixel indices)
 static PointCloudRGB::Ptr narf_keypoints(const PointCloudRGB::Ptr& cloud, PointCloud<int>::Ptr& keypoints) {
   int image_size_x = 640, image_size_y = 480;
   float center_x = (640.0f / 2.0f), center_y = (480.0f / 2.0f);
   float focal_length_x = 525.0f;
-  Eigen::Affine3f sensor_pose = Eigen::Affine3f(Eigen::Translation3f(cloud->sensor_origin_[0],
-                                                                     cloud->sensor_origin_[1],
-                                                                     cloud->sensor_origin_[2])) *
-                                Eigen::Affine3f(cloud->sensor_orientation_);
+  Eigen::Affine3f sensor_pose = sensor_pose_of(*cloud);
   float noise_level = 0.0f, minimum_range = 0.0f;
   RangeImagePlanar range_image;
   range_image.createFromPointCloudWithFixedSize(*cloud, image_size_x, image_size_y, center_x, center_y,
@@ -263,8 +277,31 @@ static void dump_xyz(const std::string& path, const PointCloudRGB& c) {
 
 int main(int argc, char** argv) {
   if (argc < 3) {
-    std::fprintf(stderr, "usage: %s cloud.pcd out_dir\n", argv[0]);
+    std::fprintf(stderr, "usage: %s cloud.pcd out_dir [target.pcd] | --pose cloud.pcd | --narf cloud.pcd out_dir\n",
+                 argv[0]);
     return 2;
+  }
+  const std::string mode = argv[1];
+  if (mode == "--pose" || mode == "--narf") {
+    PointCloudRGB::Ptr posed(new PointCloudRGB);
+    if (!read_pcd(argv[2], *posed) || (mode == "--narf" && argc < 4)) {
+      std::fprintf(stderr, "cannot read %s\n", argv[2]);
+      return 2;
+    }
+    if (mode == "--pose") {  // the 16 floats of the pose (host only: no device call), as raw bits
+      const Eigen::Affine3f pose = sensor_pose_of(*posed);
+      for (int i = 0; i < 16; ++i) {
+        uint32_t b;
+        std::memcpy(&b, &pose.m[i], sizeof(b));
+        std::printf("%08x%c", b, i == 15 ? '\n' : ' ');
+      }
+      return 0;
+    }
+    PointCloud<int>::Ptr kp;  // the NARF branch alone
+    narf_keypoints(posed, kp);
+    dump(std::string(argv[3]) + "/keypoints.i32", kp->points.data(), kp->points.size());
+    std::printf("points %zu keypoints %zu\n", posed->size(), kp->size());
+    return 0;
   }
   PointCloudRGB::Ptr cloud(new PointCloudRGB);
   if (!read_pcd(argv[1], *cloud)) {

@@ -1,7 +1,9 @@
 """The C++ PCL-compatible facade (include/pfx_pcl.hpp): tests/cpp/facade_driver.cpp writes the
 reference's NARF + Features<T> flow (keypoints.h:199-231, features.h:175-196, tools.h:22-32) against
 it.  CPU: the driver compiles and links against libpfx.so.  GPU: its outputs equal the Python
-C-ABI path (itself bit-exact against the oracle) on a reference cloud."""
+C-ABI path (itself bit-exact against the oracle) on a reference cloud.  A PCD with a VIEWPOINT other
+than the identity goes through the facade's Affine3f(Translation3f) * Affine3f(Quaternionf): the
+pose's 16 floats on the CPU, the NARF keypoints at that pose against the oracle on the GPU."""
 import os
 import subprocess
 
@@ -27,6 +29,50 @@ def build_driver():
 def test_facade_compiles_and_links():
     exe = build_driver()
     assert os.access(exe, os.X_OK)
+
+
+def _posed_pcd(tmp_path, x, y, z):
+    """The points moved by the general pose H (narf_cases.POSES), in a PCD whose VIEWPOINT carries
+    H's translation and unit quaternion; returns (path, the pose as the facade builds it)."""
+    import narf_cases as C
+    import pcd_cases
+    m = C.POSES["H"]
+    t, q = m[:3, 3].astype(np.float32), pcd_cases.quaternion_of(m[:3, :3])
+    p = np.stack([x, y, z]).astype(np.float64)
+    moved = (m[:3, :3] @ p + m[:3, 3:4]).astype(np.float32)
+    path = tmp_path / "posed.pcd"
+    pcd_cases.write_binary_xyzrgb(path, moved[0], moved[1], moved[2], viewpoint=(*t, *q))
+    return path, moved, pcd_cases.viewpoint_pose(t, q)
+
+
+def test_facade_pose_from_viewpoint(tmp_path):
+    """The shim alone (no device): VIEWPOINT -> sensor_origin_ / sensor_orientation_ -> the pose."""
+    import narf_cases as C
+    exe = build_driver()
+    r = np.random.default_rng(5).normal(0, 1, (3, 50)).astype(np.float32)
+    path, _, want = _posed_pcd(tmp_path, *r)
+    out = subprocess.run([exe, "--pose", str(path)], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr
+    got = np.array([int(v, 16) for v in out.stdout.split()], np.uint32)
+    assert np.array_equal(got, want.ravel().view(np.uint32))
+    # it is H up to float32 rounding, and a rigid pose with a real rotation about every axis
+    assert np.allclose(want, C.POSES["H"], atol=1e-6) and np.all(np.abs(want[:3, :3]) > 0.05)
+
+
+@pytest.mark.gpu
+def test_facade_posed_pcd_matches_oracle(tmp_path):
+    import oracle_lib as O
+    from pcl_feature_extraction_amd.pcd import read_pcd
+    exe = build_driver()
+    c = read_pcd(PCD)
+    path, moved, pose = _posed_pcd(tmp_path, c.x, c.y, c.z)
+    r = subprocess.run([exe, "--narf", str(path), str(tmp_path)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    kp = np.fromfile(tmp_path / "keypoints.i32", np.int32)
+    okp = O.narf_keypoints(moved[0], moved[1], moved[2], cam=dict(sensor_pose=pose))
+    assert len(okp) >= 5 and np.array_equal(kp, okp)
+    # the pose matters: with the identity the moved cloud gives other keypoints
+    assert not np.array_equal(okp, O.narf_keypoints(moved[0], moved[1], moved[2]))
 
 
 @pytest.mark.gpu
