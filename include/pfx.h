@@ -21,6 +21,8 @@
  *                          Features<T>::compute (features.h:175-196, evaluation.cpp:593-612)
  *   pfx_shot*           <- SHOTEstimationOMP<PointXYZRGB,Normal,SHOT352>::compute
  *                          (features.h:175-196, evaluation.cpp:766-785)
+ *   pfx_shot_color*     <- SHOTColorEstimationOMP<PointXYZRGB,Normal,SHOT1344>::compute
+ *                          (features.h:175-196, evaluation.cpp:786-805)
  *   pfx_pfh*            <- PFHEstimation<PointXYZRGB,Normal,PFHSignature125>::compute
  *                          (features.h:175-196, evaluation.cpp:676-695)
  *   pfx_range_image_planar* <- RangeImagePlanar::createFromPointCloudWithFixedSize
@@ -322,6 +324,31 @@ pfx_status pfx_shot_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, cons
                         const float* d_qz, int64_t nq, double radius, float* d_desc,
                         float* d_rf);
 
+/* ---- SHOT-1344: SHOTColorEstimationOMP (evaluation.cpp:786-805) ----------------------- */
+/* The shape and colour descriptor (describe_shape and describe_color both on, PCL's defaults).
+ * srgb / qrgb: one packed 0x00RRGGBB word per surface point / per query (PointXYZRGB::rgba; only
+ * the low 24 bits are read).  The reference colour of a query is qrgb's, as PCL takes it from the
+ * input cloud, not from the surface.  desc: nq x 1344 -- desc[v * 11 + s] is shape volume v
+ * (0..31), slot s (0..10); desc[352 + v * 31 + s] is colour slot s (0..30) of volume v.  rf:
+ * nq x 9, equal to pfx_shot's bit for bit; neighbours, frame and NaN rows follow pfx_shot's rules,
+ * and so does the capacity (more than 16384 neighbours: PFX_ERR_CAPACITY).  radius <= 0 or a null
+ * pointer: PFX_ERR_INVALID.  RGB2CIELAB reads its sXYZ table one past the end for pure white in
+ * PCL; here that index is clamped to the last entry.  Statistics of the last call:
+ * "shot_color_neighbors" (sum of the neighbourhood sizes), "shot_color_lut_clamped" (surface
+ * points plus queries whose table index was clamped); "shot_color_cap_small" (the longest list of
+ * the split kernels; longer ones take the one-workgroup path) can be read from a new ctx. */
+pfx_status pfx_shot_color(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz,
+                          const float* snx, const float* sny, const float* snz, const uint32_t* srgb,
+                          int64_t n_surface, const float* qx, const float* qy, const float* qz,
+                          const uint32_t* qrgb, int64_t nq, double radius, float* desc, float* rf);
+/* Device pointers, stream-ordered on the ctx stream like pfx_shot_dev (one host wait at the end,
+ * for the capacity check and the statistics). */
+pfx_status pfx_shot_color_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                              const float* d_snx, const float* d_sny, const float* d_snz,
+                              const uint32_t* d_srgb, int64_t n_surface, const float* d_qx,
+                              const float* d_qy, const float* d_qz, const uint32_t* d_qrgb, int64_t nq,
+                              double radius, float* d_desc, float* d_rf);
+
 /* ---- PFH-125: PFHEstimation (surface + normals, queries = input cloud) ---------------- */
 /* out: nq x 125 row-major (PFHSignature125::histogram): every pair of a query's radius
  * neighbourhood binned 5 x 5 x 5, each hit adding 100 / (k (k - 1) / 2); a non-finite query or
@@ -389,7 +416,8 @@ pfx_status pfx_gather_points_dev(pfx_ctx* ctx, const float* d_x, const float* d_
                                  float* d_kx, float* d_ky, float* d_kz, int64_t cap, int64_t* n_out);
 
 /* Descriptor matching.  Rows are `dim` floats, `*_stride` floats apart
- * (FPFHSignature33: dim 33, stride 33; PointCloud<SHOT352> read in place: dim 352, stride 361).
+ * (FPFHSignature33: dim 33, stride 33; PointCloud<SHOT352> read in place: dim 352, stride 361;
+ * PointCloud<SHOT1344>: dim 1344, stride 1353).
  * Distance = FLANN L2_Simple<float> (sequential float sum of squared differences), exact 1-NN;
  * equal distances -> the lowest row (FLANN: first visited, unpinned); a source row with a
  * non-finite value, or no finite target row -> -1 and NaN distance.

@@ -8,6 +8,7 @@
 //                                                       search::KdTree, setRadiusSearch, compute
 //   include/pcl_feature_extraction/tools.h:22-32        NormalEstimationOMP
 //   src/evaluation.cpp:593-612, :676-695, :766-785      FPFHEstimation, PFHEstimation, SHOTEstimationOMP
+//   src/evaluation.cpp:786-805                           SHOTColorEstimationOMP
 //   include/pcl_feature_extraction/features.h:224-273   KdTreeFLANN<FeatureT>::nearestKSearch,
 //                                                       Correspondence(s), boost::thread / ref
 // This header provides those names in namespace pcl (plus the minimal Eigen subset the calls
@@ -187,6 +188,7 @@ struct alignas(16) PointXYZI {
 struct FPFHSignature33 { float histogram[33]; };
 struct PFHSignature125 { float histogram[125]; };
 struct SHOT352 { float descriptor[352]; float rf[9]; };
+struct SHOT1344 { float descriptor[1344]; float rf[9]; };
 struct ReferenceFrame { float x_axis[3], y_axis[3], z_axis[3]; };
 
 template <typename T>
@@ -429,6 +431,46 @@ class SHOTEstimationOMP : public FeatureFromNormals<PointInT, PointNT, PointOutT
       for (int b = 0; b < 352; ++b) out.points[i].descriptor[b] = d[i * 352 + b];
       for (int b = 0; b < 9; ++b) out.points[i].rf[b] = rf[i * 9 + b];
       if (std::isnan(d[i * 352])) out.is_dense = false;
+    }
+  }
+};
+
+// SHOTColorEstimationOMP<In, Normal, SHOT1344> (evaluation.cpp:790): shape and colour, PCL's
+// defaults.  The colours are the low 24 bits of rgba, the surface's for the neighbours and the
+// input cloud's for the reference colour of each query.
+template <typename PointInT, typename PointNT, typename PointOutT = SHOT1344,
+          typename PointRFT = ReferenceFrame>
+class SHOTColorEstimationOMP : public FeatureFromNormals<PointInT, PointNT, PointOutT> {
+ public:
+  typedef std::shared_ptr<SHOTColorEstimationOMP<PointInT, PointNT, PointOutT, PointRFT> > Ptr;
+  explicit SHOTColorEstimationOMP(unsigned int /*nr_threads*/ = 0) { this->name_ = "SHOTColorEstimationOMP"; }
+  void setNumberOfThreads(unsigned int) {}
+
+ protected:
+  void computeFeature(PointCloud<PointOutT>& out) override {
+    const PointCloud<PointInT>& surf = this->surface();
+    if (!this->normals_ || this->normals_->size() != surf.size()) {
+      PCL_ERROR("[pcl::SHOTColorEstimationOMP::compute] normals missing or not matching the surface\n");
+      return;
+    }
+    const detail::SoA s = detail::soa_xyz(surf), nrm = detail::soa_normals(*this->normals_);
+    const detail::SoA q = detail::soa_xyz(*this->input_);
+    const size_t ns = surf.size(), nq = this->input_->size();
+    std::vector<uint32_t> srgb(ns + 1), qrgb(nq + 1);
+    for (size_t i = 0; i < ns; ++i) srgb[i] = surf.points[i].rgba & 0x00ffffffu;
+    for (size_t i = 0; i < nq; ++i) qrgb[i] = this->input_->points[i].rgba & 0x00ffffffu;
+    std::vector<float> d(nq * 1344), rf(nq * 9);
+    if (!detail::ok(pfx_shot_color(detail::context(), s.x.data(), s.y.data(), s.z.data(), nrm.x.data(),
+                                   nrm.y.data(), nrm.z.data(), srgb.data(), (int64_t)ns, q.x.data(), q.y.data(),
+                                   q.z.data(), qrgb.data(), (int64_t)nq, this->search_radius_, d.data(), rf.data()),
+                    "SHOTColorEstimationOMP"))
+      return;
+    out.resize(nq);
+    out.is_dense = true;
+    for (size_t i = 0; i < nq; ++i) {
+      for (int b = 0; b < 1344; ++b) out.points[i].descriptor[b] = d[i * 1344 + b];
+      for (int b = 0; b < 9; ++b) out.points[i].rf[b] = rf[i * 9 + b];
+      if (std::isnan(d[i * 1344])) out.is_dense = false;
     }
   }
 };
@@ -773,6 +815,7 @@ namespace detail {
 template <typename T> struct DescriptorLayout;
 template <> struct DescriptorLayout<FPFHSignature33> { static constexpr int dim = 33, stride = 33; };
 template <> struct DescriptorLayout<SHOT352> { static constexpr int dim = 352, stride = 361; };
+template <> struct DescriptorLayout<SHOT1344> { static constexpr int dim = 1344, stride = 1353; };
 template <> struct DescriptorLayout<PFHSignature125> { static constexpr int dim = 125, stride = 125; };
 }  // namespace detail
 

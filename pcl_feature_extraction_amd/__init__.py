@@ -1,6 +1,6 @@
 """pcl_feature_extraction_amd -- MI355X-native (gfx950) hot path of srv/pcl_feature_extraction.
 
-NARF keypoints on the planar range image + normals + FPFH-33 / SHOT-352 / PFH-125 descriptors over radius
+NARF keypoints on the planar range image + normals + FPFH-33 / SHOT-352 / SHOT-1344 / PFH-125 descriptors over radius
 neighbourhoods, as hand-written HIP kernels behind the C-ABI in include/pfx.h (libpfx.so).
 See DESIGN.md.
 """

@@ -112,6 +112,10 @@ _SIGS = {
                          c_dbl, c_vp, c_vp]),
     "pfx_shot_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,
                              c_i64, c_dbl, c_vp, c_vp]),
+    "pfx_shot_color": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64,
+                               c_dbl, c_vp, c_vp]),
+    "pfx_shot_color_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                   c_i64, c_dbl, c_vp, c_vp]),
     "pfx_pfh": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl, c_vp]),
     "pfx_pfh_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
                             c_vp]),

@@ -16,6 +16,14 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _u32(a):
+    """Packed 0x00RRGGBB colour words; int32 input keeps its bits."""
+    a = np.asarray(a)
+    if a.dtype == np.int32:
+        a = a.view(np.uint32)
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
 def _ptr(a):
     if a is None:
         return None
@@ -180,6 +188,21 @@ class Context:
                                        _ptr(qx), _ptr(qy), _ptr(qz), nq, float(r), _ptr(desc), _ptr(rf)))
         return desc, rf
 
+    def shot_color(self, sx, sy, sz, nx, ny, nz, srgb, qx, qy, qz, qrgb, r):
+        """SHOTColorEstimationOMP (pfx_shot_color): srgb / qrgb are packed 0x00RRGGBB words (the low
+        24 bits are read); returns desc (nq, 1344) and rf (nq, 9) float32."""
+        sx, sy, sz, nx, ny, nz, qx, qy, qz = map(_f32, (sx, sy, sz, nx, ny, nz, qx, qy, qz))
+        srgb, qrgb = _u32(srgb), _u32(qrgb)
+        if len(srgb) != len(sx) or len(qrgb) != len(qx):
+            raise ValueError("shot_color: one packed colour per surface point and per query")
+        nq = len(qx)
+        desc = np.empty((nq, 1344), dtype=np.float32)
+        rf = np.empty((nq, 9), dtype=np.float32)
+        self._check(self._lib.pfx_shot_color(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(nx), _ptr(ny), _ptr(nz),
+                                             _ptr(srgb), len(sx), _ptr(qx), _ptr(qy), _ptr(qz), _ptr(qrgb), nq,
+                                             float(r), _ptr(desc), _ptr(rf)))
+        return desc, rf
+
     def pfh(self, sx, sy, sz, nx, ny, nz, qx, qy, qz, r):
         """PFHEstimation (pfx_pfh): (nq, 125) float32, NaN rows for queries without neighbours."""
         sx, sy, sz, nx, ny, nz, qx, qy, qz = map(_f32, (sx, sy, sz, nx, ny, nz, qx, qy, qz))
@@ -329,6 +352,17 @@ class Context:
         self._check(self._lib.pfx_shot_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(nx), _ptr(ny), _ptr(nz),
                                            sx.numel(), _ptr(qx), _ptr(qy), _ptr(qz), qx.numel(), float(r),
                                            _ptr(desc), _ptr(rf)))
+
+    def shot_color_dev(self, sx, sy, sz, nx, ny, nz, srgb, qx, qy, qz, qrgb, r, desc, rf):
+        """pfx_shot_color_dev: srgb / qrgb are 32-bit integer device tensors of packed 0x00RRGGBB words,
+        desc (nq, 1344) and rf (nq, 9) float32 device tensors."""
+        if srgb.element_size() != 4 or qrgb.element_size() != 4:
+            raise ValueError("shot_color_dev: the packed colours must be 32-bit words")
+        if srgb.numel() != sx.numel() or qrgb.numel() != qx.numel():
+            raise ValueError("shot_color_dev: one packed colour per surface point and per query")
+        self._check(self._lib.pfx_shot_color_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(nx), _ptr(ny), _ptr(nz),
+                                                 _ptr(srgb), sx.numel(), _ptr(qx), _ptr(qy), _ptr(qz), _ptr(qrgb),
+                                                 qx.numel(), float(r), _ptr(desc), _ptr(rf)))
 
     def pfh_dev(self, sx, sy, sz, nx, ny, nz, qx, qy, qz, r, out):
         """pfx_pfh_dev: out is an (nq, 125) float32 device tensor; no host synchronisation (a

@@ -106,6 +106,7 @@ pfx_status pfx_ctx_create(int device, pfx_ctx** out) {
     PFX_HIP(hipSetDevice(device));
     ctx->on_own_stream = true;  // created on first use (check_ctx)
     ctx->stats["pfh_cap_lds"] = pfx::pfh_cap_lds();
+    ctx->stats["shot_color_cap_small"] = pfx::shot_color_cap_small();
     // grid builds by builder (pfx_grid.hip), and speculative counting builds that met a fat cell
     for (const char* s : {"grid_count_builds", "grid_sort_builds", "grid_hinted_sort_builds", "grid_fat_fallbacks"})
       ctx->stats[s] = 0;
@@ -573,6 +574,55 @@ pfx_status pfx_shot(pfx_ctx* ctx, const float* sx, const float* sy, const float*
   pfx::shot_dev(ctx, dsx, dsy, dsz, dnx, dny, dnz, n_surface, dqx, dqy, dqz, nq, radius, ddesc, drf);
   if (nq) {
     PFX_HIP(hipMemcpyAsync(desc, ddesc, sizeof(float) * nq * 352, hipMemcpyDeviceToHost, ctx->stream));
+    PFX_HIP(hipMemcpyAsync(rf, drf, sizeof(float) * nq * 9, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_shot_color_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                              const float* d_snx, const float* d_sny, const float* d_snz,
+                              const uint32_t* d_srgb, int64_t n_surface, const float* d_qx,
+                              const float* d_qy, const float* d_qz, const uint32_t* d_qrgb, int64_t nq,
+                              double radius, float* d_desc, float* d_rf) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  if (n_surface < 0 || nq < 0 || !(radius > 0.0) ||
+      (nq && (!d_desc || !d_rf || !d_qx || !d_qy || !d_qz || !d_qrgb)) ||
+      (n_surface && (!d_sx || !d_sy || !d_sz || !d_snx || !d_sny || !d_snz || !d_srgb)))
+    throw Error(PFX_ERR_INVALID, "shot_color: invalid arguments");
+  pfx::shot_color_dev(ctx, d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, d_srgb, n_surface, d_qx, d_qy, d_qz, d_qrgb, nq,
+                      radius, d_desc, d_rf);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_shot_color(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
+                          const float* sny, const float* snz, const uint32_t* srgb, int64_t n_surface,
+                          const float* qx, const float* qy, const float* qz, const uint32_t* qrgb, int64_t nq,
+                          double radius, float* desc, float* rf) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!desc || !rf || !qx || !qy || !qz || !qrgb)) ||
+      (n_surface && (!sx || !sy || !sz || !snx || !sny || !snz || !srgb)))
+    throw Error(PFX_ERR_INVALID, "shot_color: invalid arguments");
+  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
+  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
+  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
+  float* dnx = stage_in(ctx, "in_nx", snx, n_surface);
+  float* dny = stage_in(ctx, "in_ny", sny, n_surface);
+  float* dnz = stage_in(ctx, "in_nz", snz, n_surface);
+  // (the packed colours are staged as the 32-bit words they are)
+  float* drgb = stage_in(ctx, "in_rgb", reinterpret_cast<const float*>(srgb), n_surface);
+  float* dqx = stage_in(ctx, "in_qx", qx, nq);
+  float* dqy = stage_in(ctx, "in_qy", qy, nq);
+  float* dqz = stage_in(ctx, "in_qz", qz, nq);
+  float* dqrgb = stage_in(ctx, "in_qrgb", reinterpret_cast<const float*>(qrgb), nq);
+  float* ddesc = ctx->buf("out_shot_color").as<float>(nq * 1344 + 1);
+  float* drf = ctx->buf("out_rf").as<float>(nq * 9 + 1);
+  pfx::shot_color_dev(ctx, dsx, dsy, dsz, dnx, dny, dnz, reinterpret_cast<const uint32_t*>(drgb), n_surface, dqx, dqy,
+                      dqz, reinterpret_cast<const uint32_t*>(dqrgb), nq, radius, ddesc, drf);
+  if (nq) {
+    PFX_HIP(hipMemcpyAsync(desc, ddesc, sizeof(float) * nq * 1344, hipMemcpyDeviceToHost, ctx->stream));
     PFX_HIP(hipMemcpyAsync(rf, drf, sizeof(float) * nq * 9, hipMemcpyDeviceToHost, ctx->stream));
   }
   PFX_HIP(hipStreamSynchronize(ctx->stream));

@@ -334,6 +334,12 @@ void fpfh_prepare_dev(pfx_ctx* ctx, const float* sx, const float* sy, const floa
 bool fpfh_validate_grid(pfx_ctx* ctx);
 void fpfh_prepare_queries_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns,
                               const float* qx, const float* qy, const float* qz, int64_t nq, double r);
+// pfx_shot_color.hip
+int64_t shot_color_cap_small();
+void shot_color_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
+                    const float* sny, const float* snz, const uint32_t* srgb, int64_t ns, const float* qx,
+                    const float* qy, const float* qz, const uint32_t* qrgb, int64_t nq, double r, float* desc,
+                    float* rf);
 void shot_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
               const float* sny, const float* snz, int64_t ns, const float* qx, const float* qy,
               const float* qz, int64_t nq, double r, float* desc, float* rf);
