@@ -43,6 +43,8 @@
  *                          (Keypoints::compute's HARRIS_3D branch, keypoints.h:150-162, 365-395)
  *   pfx_ransac_rejector <- registration::CorrespondenceRejectorSampleConsensus<PointXYZRGB> in
  *                          Features<T>::filterCorrespondences (features.h:282-297)
+ *   pfx_icp*            <- IterativeClosestPoint<PointXYZRGB,PointXYZRGB>::align in icpAlign
+ *                          (evaluation.cpp:863-885)
  * ===================================================================================== */
 #ifndef PFX_H_
 #define PFX_H_
@@ -530,6 +532,54 @@ pfx_status pfx_ransac_rejector(pfx_ctx* ctx, const float* sx, const float* sy, c
                                const float* tx, const float* ty, const float* tz, int64_t nt, const int32_t* query,
                                const int32_t* match, int64_t n, double threshold, int32_t max_iterations,
                                int32_t* keep, int64_t* n_keep, float* transformation);
+
+/* ---- ICP alignment (evaluation.cpp:863-885, icpAlign) --------------------------------- */
+/* pcl::IterativeClosestPoint<PointXYZRGB,PointXYZRGB>::align as PCL 1.7.2 runs it with its
+ * defaults (correspondence estimation without reciprocity, no rejectors, Umeyama's fit in float,
+ * DefaultConvergenceCriteria), restated in DESIGN.md "ICP: the contract"; results equal the CPU
+ * restatement tests/cpp/icp_ref.cpp bit for bit, parity with real PCL is unpinned.
+ * pfx_icp_params_default fills PCL's defaults: sqrt(DBL_MAX), 10, 0, -DBL_MAX (the reference sets
+ * 0.07, 100, 1e-6, 1e-4).  Sigma is accumulated over depth blocks of PFX_ICP_GEMM_DEPTH
+ * correspondences (Eigen 3.2's GEMM panel for a 32 KiB L1). */
+#define PFX_ICP_GEMM_DEPTH 1024
+typedef struct pfx_icp_params {
+  double max_correspondence_distance; /* setMaxCorrespondenceDistance, > 0                     */
+  int32_t max_iterations;             /* setMaximumIterations, >= 0 (0 still runs one)         */
+  double transformation_epsilon;      /* setTransformationEpsilon                              */
+  double euclidean_fitness_epsilon;   /* setEuclideanFitnessEpsilon                            */
+} pfx_icp_params;
+void pfx_icp_params_default(pfx_icp_params* p);
+/* DefaultConvergenceCriteria's state after align; PFX_ICP_NO_CORRESPONDENCES: fewer than 3 pairs */
+enum {
+  PFX_ICP_NOT_CONVERGED = 0,
+  PFX_ICP_ITERATIONS = 1,
+  PFX_ICP_TRANSFORM = 2,
+  PFX_ICP_ABS_MSE = 3,
+  PFX_ICP_REL_MSE = 4,
+  PFX_ICP_NO_CORRESPONDENCES = 5
+};
+/* Source and target clouds as SoA floats (non-finite points are skipped); guess: row-major 4x4 or
+ * NULL for the identity.  Outputs (host, in both entry points): transformation[16] row-major
+ * (getFinalTransformation), *fitness (getFitnessScore(): mean squared distance of every finite
+ * transformed source point to its nearest target point, DBL_MAX without any), *converged
+ * (hasConverged), *iterations, *state.  ax/ay/az (nullable, ns floats each; device memory for
+ * pfx_icp_dev): the aligned source cloud, i.e. the cloud align() hands back.  Both calls return
+ * after the last iteration (one host synchronisation per iteration, two where the mean squared
+ * error cannot be summed exactly in parallel and one lane runs PCL's loop).  A null pointer, a negative
+ * count, max_correspondence_distance <= 0, max_iterations < 0 or a NaN parameter:
+ * PFX_ERR_INVALID.  Statistics: "icp_iterations", "icp_state", "icp_correspondences" (last
+ * iteration), "icp_nn_rounds" (most grid rounds one search needed), "icp_brute" (queries that fell
+ * to the exhaustive scan, whole call), "icp_exact_sum" (1: every double sum took the exact
+ * integer route). */
+pfx_status pfx_icp(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, const float* tx,
+                   const float* ty, const float* tz, int64_t nt, const pfx_icp_params* params, const float* guess,
+                   float* transformation, double* fitness, int32_t* converged, int32_t* iterations, int32_t* state,
+                   float* ax, float* ay, float* az);
+pfx_status pfx_icp_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz, int64_t ns,
+                       const float* d_tx, const float* d_ty, const float* d_tz, int64_t nt,
+                       const pfx_icp_params* params, const float* guess, float* transformation, double* fitness,
+                       int32_t* converged, int32_t* iterations, int32_t* state, float* d_ax, float* d_ay,
+                       float* d_az);
 
 /* ---- multi-GPU scan batch (SURVEY 8(e), configs[4]) ------------------------------------- */
 /* Replaces the reference's per-scan loop for the (Narf, FPFH) pair (evaluation.cpp:272-852 over

@@ -9,6 +9,7 @@
 //   include/pcl_feature_extraction/tools.h:22-32        NormalEstimationOMP
 //   src/evaluation.cpp:593-612, :676-695, :766-785      FPFHEstimation, PFHEstimation, SHOTEstimationOMP
 //   src/evaluation.cpp:786-805                           SHOTColorEstimationOMP
+//   src/evaluation.cpp:863-885, :257                     IterativeClosestPoint, transformPointCloud
 //   include/pcl_feature_extraction/features.h:224-273   KdTreeFLANN<FeatureT>::nearestKSearch,
 //                                                       Correspondence(s), boost::thread / ref
 // This header provides those names in namespace pcl (plus the minimal Eigen subset the calls
@@ -993,6 +994,95 @@ class CorrespondenceRejectorSampleConsensus {
   Eigen::Matrix4f best_;
 };
 }  // namespace registration
+
+// ---- ICP alignment (evaluation.cpp:863-885, 257) ------------------------------------------------
+// transformPointCloud(in, out, Matrix4f): every finite point under the affine part of the matrix,
+// ((R_i0 x + R_i1 y) + R_i2 z) + t_i in float (on a target with fused multiply-add, build with
+// -ffp-contract=off to keep this order); the other fields are copied
+template <typename PointT>
+inline void transformPointCloud(const PointCloud<PointT>& in, PointCloud<PointT>& out, const Eigen::Matrix4f& T) {
+  if (&in != &out) out = in;
+  for (auto& p : out.points) {
+    if (!(std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z))) continue;
+    const float x = p.x, y = p.y, z = p.z;
+    p.x = ((T(0, 0) * x + T(0, 1) * y) + T(0, 2) * z) + T(0, 3);
+    p.y = ((T(1, 0) * x + T(1, 1) * y) + T(1, 2) * z) + T(1, 3);
+    p.z = ((T(2, 0) * x + T(2, 1) * y) + T(2, 2) * z) + T(2, 3);
+  }
+}
+
+// IterativeClosestPoint<PointSource, PointTarget>: PCL 1.7.2's defaults (no reciprocal
+// correspondences, no rejectors, Umeyama's fit, DefaultConvergenceCriteria), the whole loop on the
+// GPU (pfx_icp).  The RANSAC outlier threshold is stored and unused, as in PCL's align().
+template <typename PointSource, typename PointTarget, typename Scalar = float>
+class IterativeClosestPoint {
+ public:
+  typedef PointCloud<PointSource> PointCloudSource;
+  typedef PointCloud<PointTarget> PointCloudTarget;
+  typedef typename PointCloudSource::ConstPtr PointCloudSourceConstPtr;
+  typedef typename PointCloudTarget::ConstPtr PointCloudTargetConstPtr;
+  IterativeClosestPoint() { pfx_icp_params_default(&params_); }
+  void setInputSource(const PointCloudSourceConstPtr& c) { source_ = c; }
+  void setInputTarget(const PointCloudTargetConstPtr& c) { target_ = c; }
+  void setMaxCorrespondenceDistance(double d) { params_.max_correspondence_distance = d; }
+  void setRANSACOutlierRejectionThreshold(double t) { ransac_threshold_ = t; }
+  void setTransformationEpsilon(double e) { params_.transformation_epsilon = e; }
+  void setEuclideanFitnessEpsilon(double e) { params_.euclidean_fitness_epsilon = e; }
+  void setMaximumIterations(int n) { params_.max_iterations = n; }
+  double getMaxCorrespondenceDistance() const { return params_.max_correspondence_distance; }
+  double getRANSACOutlierRejectionThreshold() const { return ransac_threshold_; }
+  double getTransformationEpsilon() const { return params_.transformation_epsilon; }
+  double getEuclideanFitnessEpsilon() const { return params_.euclidean_fitness_epsilon; }
+  int getMaximumIterations() const { return params_.max_iterations; }
+  void align(PointCloudSource& output) { align(output, Eigen::Matrix4f::Identity()); }
+  void align(PointCloudSource& output, const Eigen::Matrix4f& guess) {
+    final_.setIdentity();
+    converged_ = false;
+    fitness_ = std::numeric_limits<double>::max();
+    state_ = PFX_ICP_NOT_CONVERGED;
+    if (!source_ || !target_) {
+      PCL_ERROR("[pcl::IterativeClosestPoint::align] no input source or target\n");
+      return;
+    }
+    output = *source_;
+    if (!detail::context()) return;
+    const detail::SoA s = detail::soa_xyz(*source_), t = detail::soa_xyz(*target_);
+    const size_t n = s.x.size();
+    std::vector<float> ax(n + 1), ay(n + 1), az(n + 1);
+    float T[16];
+    int32_t conv = 0, it = 0, state = 0;
+    std::lock_guard<std::mutex> lock(detail::context_mutex());
+    if (!detail::ok(pfx_icp(detail::context(), s.x.data(), s.y.data(), s.z.data(), (int64_t)n, t.x.data(), t.y.data(),
+                            t.z.data(), (int64_t)t.x.size(), &params_, guess.m, T, &fitness_, &conv, &it, &state,
+                            ax.data(), ay.data(), az.data()),
+                    "IterativeClosestPoint"))
+      return;
+    for (size_t i = 0; i < n; ++i) {
+      output.points[i].x = ax[i];
+      output.points[i].y = ay[i];
+      output.points[i].z = az[i];
+    }
+    for (int i = 0; i < 16; ++i) final_.m[i] = T[i];
+    converged_ = conv != 0;
+    state_ = state;
+  }
+  Eigen::Matrix4f getFinalTransformation() const { return final_; }
+  // the mean squared distance of the aligned source to the target, without a distance cap
+  double getFitnessScore() const { return fitness_; }
+  bool hasConverged() const { return converged_; }
+  // DefaultConvergenceCriteria::getConvergenceState() of the last align (PFX_ICP_*)
+  int getConvergenceState() const { return state_; }
+
+ private:
+  PointCloudSourceConstPtr source_;
+  PointCloudTargetConstPtr target_;
+  pfx_icp_params params_;
+  double ransac_threshold_ = 0.05;
+  Eigen::Matrix4f final_;
+  double fitness_ = std::numeric_limits<double>::max();
+  bool converged_ = false;
+  int state_ = PFX_ICP_NOT_CONVERGED;
+};
 
 }  // namespace pcl
 

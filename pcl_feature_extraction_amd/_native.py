@@ -66,6 +66,16 @@ class PcdHeader(ctypes.Structure):
     ]
 
 
+class IcpParams(ctypes.Structure):
+    """pfx_icp_params (the IterativeClosestPoint setters of the reference's icpAlign)."""
+    _fields_ = [
+        ("max_correspondence_distance", ctypes.c_double),
+        ("max_iterations", ctypes.c_int32),
+        ("transformation_epsilon", ctypes.c_double),
+        ("euclidean_fitness_epsilon", ctypes.c_double),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "pfx_narf_params_default": (None, [ctypes.POINTER(NarfParams)]),
@@ -164,10 +174,16 @@ _SIGS = {
                                     ctypes.POINTER(NarfParams), c_dbl, c_dbl, c_vp, c_vp, c_i64, c_vp]),
     "pfx_ransac_rejector": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64,
                                     ctypes.c_double, ctypes.c_int32, c_vp, c_i64p, c_vp]),
+    "pfx_icp_params_default": (None, [ctypes.POINTER(IcpParams)]),
+    "pfx_icp": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(IcpParams), c_vp, c_vp,
+                        ctypes.POINTER(c_dbl), c_i32p, c_i32p, c_i32p, c_vp, c_vp, c_vp]),
+    "pfx_icp_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(IcpParams), c_vp,
+                            c_vp, ctypes.POINTER(c_dbl), c_i32p, c_i32p, c_i32p, c_vp, c_vp, c_vp]),
 }
 
-# test hooks an older library loaded through PFX_LIB (A/B runs against a previous build) may lack
-_TEST_HOOKS = {"pfx_grid_debug"}
+# entry points an older library loaded through PFX_LIB (A/B runs against a previous build) may lack:
+# test hooks, and ICP (calling a missing one raises AttributeError there)
+_OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_icp_dev"}
 
 _lib = None
 
@@ -196,7 +212,7 @@ def lib():
         for name, (res, args) in _SIGS.items():
             fn = getattr(lb, name, None)
             if fn is None:
-                if name in _TEST_HOOKS and os.environ.get("PFX_LIB"):
+                if name in _OLDER_MAY_LACK and os.environ.get("PFX_LIB"):
                     continue
                 raise AttributeError(f"{LIB_PATH} does not export {name}")
             fn.restype = res

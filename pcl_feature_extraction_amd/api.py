@@ -9,6 +9,8 @@ import ctypes
 
 import numpy as np
 
+import collections
+
 from . import _native as N
 
 
@@ -39,6 +41,25 @@ def narf_params(support_size=0.2, **kw) -> N.NarfParams:
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def icp_params(**kw) -> N.IcpParams:
+    """pfx_icp_params with PCL's defaults (sqrt(DBL_MAX), 10, 0, -DBL_MAX); the reference's icpAlign
+    sets max_correspondence_distance=0.07, max_iterations=100, transformation_epsilon=1e-6,
+    euclidean_fitness_epsilon=1e-4."""
+    p = N.IcpParams()
+    N.lib().pfx_icp_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"icp_params: unknown field {k}")
+        setattr(p, k, v)
+    return p
+
+
+#: result of Context.icp / icp_dev; state: 0 not converged, 1 iterations, 2 transform, 3 absolute
+#: MSE, 4 relative MSE, 5 no correspondences (pfx.h PFX_ICP_*); aligned: (x, y, z) or None
+IcpResult = collections.namedtuple("IcpResult",
+                                   "transformation fitness converged iterations state aligned")
 
 
 def pcd_header(path) -> N.PcdHeader:
@@ -563,6 +584,34 @@ class Context:
                                                   _ptr(tz), len(tx), _ptr(query), _ptr(match), n, threshold,
                                                   max_iterations, _ptr(keep), ctypes.byref(nk), _ptr(T)))
         return keep[: nk.value].copy(), T.reshape(4, 4)
+
+    # ---- ICP alignment (evaluation.cpp:863-885) --------------------------------------------
+    def _icp_call(self, fn, src, tgt, ns, nt, params, guess, aligned):
+        params = params or icp_params()
+        g = None if guess is None else np.ascontiguousarray(guess, np.float32).reshape(16)
+        T = np.empty(16, np.float32)
+        fit = ctypes.c_double()
+        conv, it, state = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        al = aligned if aligned is not None else (None, None, None)
+        self._check(fn(self.h, _ptr(src[0]), _ptr(src[1]), _ptr(src[2]), ns, _ptr(tgt[0]), _ptr(tgt[1]),
+                       _ptr(tgt[2]), nt, ctypes.byref(params), _ptr(g), _ptr(T), ctypes.byref(fit), ctypes.byref(conv),
+                       ctypes.byref(it), ctypes.byref(state), _ptr(al[0]), _ptr(al[1]), _ptr(al[2])))
+        return IcpResult(T.reshape(4, 4), fit.value, bool(conv.value), it.value, state.value, aligned)
+
+    def icp(self, sx, sy, sz, tx, ty, tz, params=None, guess=None, aligned=True):
+        """IterativeClosestPoint::align (pfx_icp) of the source cloud onto the target cloud (host
+        arrays): IcpResult(transformation 4x4, fitness score, converged, iterations, state, aligned
+        source cloud).  params: icp_params(...); guess: 4x4 or None."""
+        src = [_f32(v) for v in (sx, sy, sz)]
+        tgt = [_f32(v) for v in (tx, ty, tz)]
+        al = tuple(np.empty(len(src[0]), np.float32) for _ in range(3)) if aligned else None
+        return self._icp_call(self._lib.pfx_icp, src, tgt, len(src[0]), len(tgt[0]), params, guess, al)
+
+    def icp_dev(self, sx, sy, sz, tx, ty, tz, params=None, guess=None, aligned=None):
+        """pfx_icp_dev: float32 device tensors; aligned: None or three device tensors of the source's
+        length.  Returns after the last iteration (the scalars are host values)."""
+        return self._icp_call(self._lib.pfx_icp_dev, (sx, sy, sz), (tx, ty, tz), sx.numel(), tx.numel(), params,
+                              guess, aligned)
 
 
 def batch_plan(n_scans, n_devices, rows_per_scan=None):

@@ -125,6 +125,7 @@ void pfx_ctx_destroy(pfx_ctx* ctx) {
   pfx::narf_release(ctx);
   pfx::normals_release(ctx);
   pfx::keypoints_release(ctx);
+  pfx::icp_release(ctx);
   ctx->grid_a.release();
   ctx->grid_b.release();
   for (auto& kv : ctx->bufs) kv.second.release();
@@ -187,6 +188,7 @@ pfx_status pfx_ctx_trim(pfx_ctx* ctx) {
   pfx::narf_release(ctx);
   pfx::normals_release(ctx);
   pfx::keypoints_release(ctx);
+  pfx::icp_release(ctx);
   ctx->grid_a.release();
   ctx->grid_b.release();
   for (auto& kv : ctx->bufs) kv.second.release();
@@ -1131,5 +1133,79 @@ extern "C" pfx_status pfx_ransac_rejector(pfx_ctx* ctx, const float* sx, const f
   *n_keep = pfx::ransac_rejector(ctx, sx, sy, sz, ns, tx, ty, tz, nt, query, match, n, threshold, max_iterations,
                                  keep, transformation, &iters);
   ctx->stats["ransac_iterations"] = iters;
+  PFX_API_END(ctx)
+}
+
+// ---- ICP alignment (pfx_icp.hip) ----
+extern "C" void pfx_icp_params_default(pfx_icp_params* p) {
+  if (!p) return;
+  p->max_correspondence_distance = std::sqrt(std::numeric_limits<double>::max());
+  p->max_iterations = 10;
+  p->transformation_epsilon = 0.0;
+  p->euclidean_fitness_epsilon = -std::numeric_limits<double>::max();
+}
+
+namespace {
+void icp_store(const pfx::IcpResult& r, float* transformation, double* fitness, int32_t* converged,
+               int32_t* iterations, int32_t* state) {
+  std::memcpy(transformation, r.T, sizeof(r.T));
+  *fitness = r.fitness;
+  *converged = r.converged;
+  *iterations = r.iterations;
+  *state = r.state;
+}
+bool icp_args_ok(const pfx_icp_params* params, const float* transformation, const double* fitness,
+                 const int32_t* converged, const int32_t* iterations, const int32_t* state, const float* ax,
+                 const float* ay, const float* az) {
+  const int aligned = (ax != nullptr) + (ay != nullptr) + (az != nullptr);
+  return params && transformation && fitness && converged && iterations && state && (aligned == 0 || aligned == 3);
+}
+}  // namespace
+
+extern "C" pfx_status pfx_icp_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz, int64_t ns,
+                                  const float* d_tx, const float* d_ty, const float* d_tz, int64_t nt,
+                                  const pfx_icp_params* params, const float* guess, float* transformation,
+                                  double* fitness, int32_t* converged, int32_t* iterations, int32_t* state,
+                                  float* d_ax, float* d_ay, float* d_az) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  check_points(d_sx, d_sy, d_sz, ns, "icp");
+  check_points(d_tx, d_ty, d_tz, nt, "icp");
+  if (!icp_args_ok(params, transformation, fitness, converged, iterations, state, d_ax, d_ay, d_az))
+    throw Error(PFX_ERR_INVALID, "icp: invalid arguments");
+  pfx::IcpResult r;
+  pfx::icp_dev(ctx, d_sx, d_sy, d_sz, ns, d_tx, d_ty, d_tz, nt, *params, guess, r, d_ax, d_ay, d_az);
+  icp_store(r, transformation, fitness, converged, iterations, state);
+  PFX_API_END(ctx)
+}
+
+extern "C" pfx_status pfx_icp(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns,
+                              const float* tx, const float* ty, const float* tz, int64_t nt,
+                              const pfx_icp_params* params, const float* guess, float* transformation,
+                              double* fitness, int32_t* converged, int32_t* iterations, int32_t* state, float* ax,
+                              float* ay, float* az) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  check_points(sx, sy, sz, ns, "icp");
+  check_points(tx, ty, tz, nt, "icp");
+  if (!icp_args_ok(params, transformation, fitness, converged, iterations, state, ax, ay, az))
+    throw Error(PFX_ERR_INVALID, "icp: invalid arguments");
+  float* dsx = stage_in(ctx, "icp_in_sx", sx, ns);
+  float* dsy = stage_in(ctx, "icp_in_sy", sy, ns);
+  float* dsz = stage_in(ctx, "icp_in_sz", sz, ns);
+  float* dtx = stage_in(ctx, "icp_in_tx", tx, nt);
+  float* dty = stage_in(ctx, "icp_in_ty", ty, nt);
+  float* dtz = stage_in(ctx, "icp_in_tz", tz, nt);
+  float* da = ax ? ctx->buf("icp_out_aligned").as<float>(3 * (size_t)(ns + 1)) : nullptr;
+  pfx::IcpResult r;
+  pfx::icp_dev(ctx, dsx, dsy, dsz, ns, dtx, dty, dtz, nt, *params, guess, r, da, da ? da + ns : nullptr,
+               da ? da + 2 * ns : nullptr);
+  if (ax && ns) {
+    PFX_HIP(hipMemcpyAsync(ax, da, sizeof(float) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    PFX_HIP(hipMemcpyAsync(ay, da + ns, sizeof(float) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    PFX_HIP(hipMemcpyAsync(az, da + 2 * ns, sizeof(float) * ns, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  icp_store(r, transformation, fitness, converged, iterations, state);
   PFX_API_END(ctx)
 }

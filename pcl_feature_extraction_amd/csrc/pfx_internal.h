@@ -135,6 +135,7 @@ struct FpfhReadback {  // pfx_fpfh.hip
 struct NarfState;     // pfx_narf.hip
 struct NormalsState;  // pfx_normals.hip
 struct KeypointState;  // pfx_iss.hip
+struct IcpState;       // pfx_icp.hip
 
 }  // namespace pfx
 
@@ -168,6 +169,7 @@ struct pfx_ctx {
   hipEvent_t lists_gate = nullptr;       // pfx_normals_gate_dev: waited for before the next list kernels
   bool normals_fork_hint = true;         // long-list chains on the side stream (last decision)
   pfx::KeypointState* kp = nullptr;      // grids + lists of the keypoint detectors
+  pfx::IcpState* icp = nullptr;          // the target grids of the ICP search
   pfx::DevBuf& buf(const char* name) { return bufs[name]; }
   // fpfh_dev's statistics / sticky error word, copied to pinned memory in stream order and read
   // after the next synchronisation (pfx::fpfh_resolve)
@@ -303,6 +305,16 @@ int64_t iss_keypoints_dev(pfx_ctx* ctx, const float* x, const float* y, const fl
                           double non_max, int min_nb, double g21, double g32, int32_t* out, int64_t cap,
                           double* third_out);
 void keypoints_release(pfx_ctx* ctx);
+// ICP (pfx_icp.hip): synchronous; ax/ay/az nullable device arrays of ns floats
+struct IcpResult {
+  float T[16];
+  double fitness;
+  int converged, iterations, state;
+};
+void icp_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, const float* tx,
+             const float* ty, const float* tz, int64_t nt, const pfx_icp_params& p, const float* guess,
+             IcpResult& out, float* ax, float* ay, float* az);
+void icp_release(pfx_ctx* ctx);
 int64_t ransac_rejector(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns,
                         const float* tx, const float* ty, const float* tz, int64_t nt, const int32_t* query,
                         const int32_t* match, int64_t n, double threshold, int max_iterations, int32_t* keep_out,

@@ -29,6 +29,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "pfx_eigen3.h"
+#include "pfx_exact_sum.h"
 #include "pfx_internal.h"
 #include "pfx_nblist.h"
 #include "pfx_neighbors.h"
@@ -57,10 +58,6 @@ constexpr int kBruteMax = 1024;  // failed queries scanned exhaustively (one wor
 __device__ __forceinline__ void top2(float d, float& b1, float& b2) {  // the two smallest d2
   b2 = fminf(b2, fmaxf(b1, d));
   b1 = fminf(b1, d);
-}
-
-__device__ __forceinline__ int32_t grid_nfinite(const GridView& g) {
-  return g.cell_start[(int64_t)g.nx * g.ny * g.nz];  // non-finite points sort behind every cell
 }
 
 // 2nd-nearest d2 of each query from its 3x3x3 block (queue == nullptr: every finite point, in
@@ -152,148 +149,7 @@ __global__ void __launch_bounds__(64) k_nn2_brute_merge(const int32_t* __restric
   term[queue[q]] = b2 < INFINITY ? sqrtf(b2) : __int_as_float(0x7fc00000);  // nres < 2: no term
 }
 
-// Exact sum of the terms.  Per block: count, smallest positive term (its ulp exponent L_b) and
-// the integer sum in units of 2^L_b; the final pass rescales every block to the global L.
-struct ResPart {
-  unsigned long long count, isum;
-  double dsum;
-  unsigned int minbits, overflow;
-};
-struct ResAcc {
-  unsigned long long count, isum;
-  double dsum;
-  int L, exact;
-};
-
-__device__ __forceinline__ int ulp_exp(unsigned int bits) {  // exponent of the ulp of a normal float
-  return (int)((bits >> 23) & 0xff) - 150;
-}
-
-__global__ void __launch_bounds__(256) k_res_partial(const float* __restrict__ term, int64_t n,
-                                                     ResPart* __restrict__ part) {
-  __shared__ unsigned long long s_c[4], s_i[4];
-  __shared__ double s_d[4];
-  __shared__ unsigned int s_m[4], s_o[4];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  unsigned long long cnt = 0;
-  unsigned int mn = 0xffffffffu;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < n; i += stride) {
-    const float t = term[i];
-    if (isnan(t)) continue;
-    ++cnt;
-    if (t > 0.0f) mn = min(mn, __float_as_uint(t));
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    cnt += __shfl_xor(cnt, o);
-    mn = min(mn, (unsigned int)__shfl_xor((int)mn, o));
-  }
-  if (lane == 0) {
-    s_c[wv] = cnt;
-    s_m[wv] = mn;
-  }
-  __syncthreads();
-  mn = min(min(s_m[0], s_m[1]), min(s_m[2], s_m[3]));
-  const int L = mn == 0xffffffffu ? 0 : ulp_exp(mn);
-  unsigned long long is = 0;
-  double ds = 0.0;
-  unsigned int ovf = 0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < n; i += stride) {
-    const float t = term[i];
-    if (!(t > 0.0f)) continue;  // NaN (no term) and zeros add nothing
-    const unsigned int b = __float_as_uint(t);
-    const int sh = ulp_exp(b) - L;  // t = m * 2^(L + sh)
-    if (sh > 39) {
-      ovf = 1;
-      continue;
-    }
-    is += (unsigned long long)((b & 0x7fffffu) | 0x800000u) << sh;
-    ds += (double)t;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    is += __shfl_xor(is, o);
-    ds += __shfl_xor(ds, o);
-    ovf |= __shfl_xor(ovf, o);
-  }
-  if (lane == 0) {
-    s_i[wv] = is;
-    s_d[wv] = ds;
-    s_o[wv] = ovf;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    ResPart r;
-    r.count = s_c[0] + s_c[1] + s_c[2] + s_c[3];
-    r.isum = s_i[0] + s_i[1] + s_i[2] + s_i[3];  // < 2^63 each: a wrap shows in dsum below
-    r.dsum = (s_d[0] + s_d[1]) + (s_d[2] + s_d[3]);
-    r.minbits = mn;
-    r.overflow = s_o[0] | s_o[1] | s_o[2] | s_o[3];
-    part[blockIdx.x] = r;
-  }
-}
-
-// one wave: global L = min over blocks, then every block sum rescaled to 2^L (exactness checked)
-__global__ void __launch_bounds__(64) k_res_final(const ResPart* __restrict__ part, int nb, ResAcc* __restrict__ acc) {
-  const int lane = threadIdx.x;
-  unsigned int mn = 0xffffffffu;
-  for (int b = lane; b < nb; b += 64) mn = min(mn, part[b].minbits);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mn = min(mn, (unsigned int)__shfl_xor((int)mn, o));
-  const int L = mn == 0xffffffffu ? 0 : ulp_exp(mn);
-  unsigned long long cnt = 0, is = 0;
-  double ds = 0.0;
-  int bad = 0;
-  for (int b = lane; b < nb; b += 64) {
-    const ResPart r = part[b];
-    cnt += r.count;
-    ds += r.dsum;
-    if (r.overflow) bad = 1;
-    if (r.isum == 0) continue;
-    const int sh = ulp_exp(r.minbits) - L;
-    // the block sum in units of 2^L must stay below 2^53 (and its own sum must not have wrapped)
-    if (r.dsum >= ldexp(1.0, ulp_exp(r.minbits) + 62) || sh > 52 || r.isum >= (1ull << (53 - sh))) {
-      bad = 1;
-      continue;
-    }
-    is += r.isum << sh;  // < 2^53 per block, <= 16 blocks per lane: no wrap
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    cnt += __shfl_xor(cnt, o);
-    is += __shfl_xor(is, o);
-    ds += __shfl_xor(ds, o);
-    bad |= __shfl_xor(bad, o);
-  }
-  if (lane == 0) {
-    acc->count = cnt;
-    acc->isum = is;
-    acc->dsum = ds;
-    acc->L = L;
-    acc->exact = (!bad && is < (1ull << 53)) ? 1 : 0;
-  }
-}
-
-// PCL's loop verbatim: one workgroup, terms staged through LDS, one lane adds in index order
-__global__ void __launch_bounds__(256) k_res_sequential(const float* __restrict__ term, int64_t n,
-                                                        double* __restrict__ out) {
-  __shared__ float s[4096];
-  double sum = 0.0;
-  for (int64_t b = 0; b < n; b += 4096) {
-    for (int k = threadIdx.x; k < 4096; k += 256) s[k] = b + k < n ? term[b + k] : __int_as_float(0x7fc00000);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll 16
-      for (int k = 0; k < 4096; ++k) {
-        const float t = s[k];
-        if (!isnan(t)) sum += (double)t;
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = sum;
-}
+// Exact sum of the terms: pfx_exact_sum.h
 
 // Eigen 3.2.0 SelfAdjointEigenSolver<Matrix3d> eigenvalues: pfx_eigen3.h
 
@@ -606,29 +462,17 @@ double cloud_resolution_dev(pfx_ctx* ctx, const float* x, const float* y, const 
     fail = fail == qa ? qb : qa;
     h *= 2.0;
   }
-  const int nblk = (int)std::min<int64_t>(ceil_div(n, 256), 1024);
-  ResPart* part = ctx->buf("res_part").as<ResPart>(nblk);
+  ResPart* part = ctx->buf("res_part").as<ResPart>(exact_sum_blocks(n));
   ResAcc* acc = ctx->buf("res_acc").as<ResAcc>(1);
   {
     TimeScope ts(ctx, "resolution_sum");
-    k_res_partial<<<nblk, 256, 0, st>>>(term, n, part);
-    k_res_final<<<1, 64, 0, st>>>(part, nblk, acc);
-    check_launch("k_res_sum");
+    exact_sum_launch(ctx, term, n, part, acc);
   }
   ResAcc h_acc;
   PFX_HIP(hipMemcpyAsync(&h_acc, acc, sizeof(h_acc), hipMemcpyDeviceToHost, st));
   PFX_HIP(hipStreamSynchronize(st));
-  double sum = 0.0;
   const bool exact = h_acc.exact != 0;
-  if (exact) {
-    sum = std::ldexp((double)h_acc.isum, h_acc.L);
-  } else {
-    double* d = ctx->buf("res_seq").as<double>(1);
-    k_res_sequential<<<1, 256, 0, st>>>(term, n, d);
-    check_launch("k_res_sequential");
-    PFX_HIP(hipMemcpyAsync(&sum, d, sizeof(double), hipMemcpyDeviceToHost, st));
-    PFX_HIP(hipStreamSynchronize(st));
-  }
+  const double sum = exact_sum_finish(ctx, h_acc, term, n, ctx->buf("res_seq").as<double>(1));
   ctx->stats["resolution_rounds"] = rounds + 1;
   ctx->stats["resolution_brute"] = brute;
   ctx->stats["resolution_exact_sum"] = exact ? 1 : 0;

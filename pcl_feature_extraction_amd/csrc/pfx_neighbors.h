@@ -55,6 +55,11 @@ __device__ __forceinline__ int64_t xcd_block(int64_t b, int64_t nblocks) {
   return (b & 7) * (nblocks >> 3) + (b >> 3);
 }
 
+// number of finite points of a grid: they fill its sorted positions [0, nfinite)
+__device__ __forceinline__ int32_t grid_nfinite(const GridView& g) {
+  return g.cell_start[(int64_t)g.nx * g.ny * g.nz];  // non-finite points sort behind every cell
+}
+
 // The 9 candidate runs (3 contiguous z-cells each) of the 3x3x3 block around a query.
 struct Runs {
   int32_t start[9];
