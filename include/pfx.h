@@ -422,7 +422,10 @@ pfx_status pfx_gather_points_dev(pfx_ctx* ctx, const float* d_x, const float* d_
  * PointCloud<SHOT1344>: dim 1344, stride 1353).
  * Distance = FLANN L2_Simple<float> (sequential float sum of squared differences), exact 1-NN;
  * equal distances -> the lowest row (FLANN: first visited, unpinned); a source row with a
- * non-finite value, or no finite target row -> -1 and NaN distance.
+ * non-finite value, or no finite target row -> -1 and NaN distance.  Every finite row is
+ * matched, whatever its magnitude: subnormal distances keep their bits, and a row whose squared
+ * differences overflow gets the nearest row by float order (all distances +inf -> the lowest
+ * finite row, distance +inf).
  * Both directions in one pass: d_s2t[i] = nearest target row of source row i (+ its squared
  * distance), d_t2s[j] = nearest source row of target row j.  Distance and t2s outputs are
  * nullable.  Stream-ordered except for one host read of the candidate count. */

@@ -35,6 +35,9 @@
 //   the two final roundings <= 2.02 u P
 //   => e = 1.5 [(2D + 6.1) u P + (12.2 D u + 6.2 2^-16) Q] + 1e-30 (flushed denormals);
 //      x1.5: margin for evaluating e itself in fp32.
+// Finite rows whose squared norm (or product) overflows fp32 make d^ or e +-inf or NaN; such a
+// pair is unbounded and unprunable (ub = +inf, lb = -inf) and the exact pass alone decides it, so
+// only a non-finite VALUE leaves a row unmatched (tests/test_gpu_match_bound.py).
 #include <algorithm>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
@@ -298,25 +301,29 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
         urow = Urow[row];
       }
       float rmin = __uint_as_float(kInfBits);
-      float dh[2], e[2];
+      float dh[2], e[2], lb[2];
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         dh[b] = (rn2 + cn2[b]) - 2.0f * acc[a][b][r];
         const float s = rnr + cnr[b];
         e[b] = 1.5f * (c1 * (s * s) + c2 * (rnr * cnr[b])) + 1e-30f;
         const bool ok = rval && cval[b];
+        // finite rows whose norms or product overflow: d^ or e is +-inf or NaN, which bounds
+        // nothing -- the pair is unbounded (ub = +inf) and unprunable (lb = -inf), and the exact
+        // pass decides.  (|d^| + e overflowing for finite d^ and e errs to the same safe side.)
+        const bool fin = fabsf(dh[b]) + e[b] < __uint_as_float(kInfBits);
+        lb[b] = fin ? dh[b] - e[b] : -__uint_as_float(kInfBits);
         if (PASS == 0) {
-          const float ub = ok ? fmaxf(dh[b] + e[b], 0.f) : __uint_as_float(kInfBits);
+          const float ub = ok && fin ? fmaxf(dh[b] + e[b], 0.f) : __uint_as_float(kInfBits);
           rmin = fminf(rmin, ub);
           cmin[b] = fminf(cmin[b], ub);
         } else if (ok) {
-          const float lb = dh[b] - e[b];
           const int64_t col = q0 + 32 * b + l32;
-          if (lb <= __uint_as_float(urow)) {
+          if (lb[b] <= __uint_as_float(urow)) {
             const unsigned slot = atomicAdd(&ncand[0], 1u);
             if (slot < cap) crow[slot] = make_int2((int)row, (int)col);
           }
-          if (lb <= __uint_as_float(ucol[b])) {
+          if (lb[b] <= __uint_as_float(ucol[b])) {
             const unsigned slot = atomicAdd(&ncand[1], 1u);
             if (slot < cap) ccol[slot] = make_int2((int)col, (int)row);
           }
@@ -333,12 +340,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
         const float trow = fminf(__uint_as_float(urow), rmin);
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-          const float lb = dh[b] - e[b];
-          const bool em = rval && cval[b] && (lb <= trow || lb <= fminf(__uint_as_float(ucol[b]), cmin[b]));
+          const bool em = rval && cval[b] && (lb[b] <= trow || lb[b] <= fminf(__uint_as_float(ucol[b]), cmin[b]));
           const uint64_t m = __ballot(em);
           if (m) {
             const unsigned k = (unsigned)__popcll(m), pre = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-            const int4 pr = make_int4((int)row, (int)(q0 + 32 * b + l32), __float_as_int(lb), 0);
+            const int4 pr = make_int4((int)row, (int)(q0 + 32 * b + l32), __float_as_int(lb[b]), 0);
             if (staged + k <= kStage) {
               if (em) stage[staged + pre] = pr;
               staged += k;
