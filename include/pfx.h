@@ -25,6 +25,8 @@
  *                          (features.h:175-196, evaluation.cpp:786-805)
  *   pfx_pfh*            <- PFHEstimation<PointXYZRGB,Normal,PFHSignature125>::compute
  *                          (features.h:175-196, evaluation.cpp:676-695)
+ *   pfx_spin_image*     <- SpinImageEstimation<PointXYZRGB,Normal,Histogram<153>>::compute
+ *                          (evaluation.cpp:514-553)
  *   pfx_range_image_planar* <- RangeImagePlanar::createFromPointCloudWithFixedSize
  *                          (keypoints.h:212-216, tools.h:61-77)
  *   pfx_narf_keypoints* <- RangeImageBorderExtractor + NarfKeypoint::compute
@@ -370,6 +372,56 @@ pfx_status pfx_pfh_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const
                        const float* d_snx, const float* d_sny, const float* d_snz,
                        int64_t n_surface, const float* d_qx, const float* d_qy,
                        const float* d_qz, int64_t nq, double radius, float* d_out);
+
+/* ---- spin images: SpinImageEstimation (evaluation.cpp:514-553) ------------------------ */
+/* image_width W in [1, 16] (PCL's default 8: Histogram<153> = (W + 1)(2W + 1));
+ * support_angle_cos in [0, 1]; min_pts_neighb >= 0; radial / angular: only 0 is supported
+ * (anything else: PFX_ERR_UNSUPPORTED).  pfx_spin_params_default fills 8, 0.0, 0, 0, 0. */
+typedef struct pfx_spin_params {
+  int32_t image_width;
+  double support_angle_cos;
+  int32_t min_pts_neighb;
+  int32_t radial, angular;
+} pfx_spin_params;
+void pfx_spin_params_default(pfx_spin_params* p);
+/* out: nq x S floats, S = (W + 1)(2W + 1); out[alpha_bin (2W + 1) + beta_bin], alpha_bin in [0, W]
+ * the distance from the axis, beta_bin in [0, 2W] the signed height along it, both in bins of
+ * radius / W / sqrt(2).  The rotation axis of query i is (qnx, qny, qnz)[i]: the normal of the
+ * *input* cloud at that point, as PCL takes it, not the surface's.  Every radius neighbour, in
+ * FLANN order, adds four bilinear weights to a double matrix; with more than one neighbour the
+ * matrix is scaled by 1 / its sum (Eigen 3.2's summation order), then cast to float.  A NaN axis
+ * makes every cosine exactly 1.0, as libstdc++'s min / max do in PCL's clamp: such a row is finite
+ * and has mass in alpha_bin 0 only.  k <= 1 (a non-finite query has k = 0): a zero row; k > 1 with
+ * nothing contributing: a NaN row (0 x inf).  snx / sny / snz (the surface normals) are read only
+ * when support_angle_cos > 0 and may be null otherwise: a neighbour whose |cos| between the axis
+ * and its normal is below support_angle_cos is skipped; counter-directed normals are kept.
+ * Null pointers other than the optional ones, radius <= 0, W outside [1, 16], support_angle_cos
+ * outside [0, 1] or NaN, or support_angle_cos > 0 without surface normals: PFX_ERR_INVALID before
+ * any launch.  Where PCL throws -- fewer than min_pts_neighb neighbours, or a cosine beyond
+ * 1 + 10 FLT_EPSILON in magnitude (an axis or normal not of unit length) -- the call returns
+ * PFX_ERR_INVALID after the kernel, pfx_last_error names the first offending query row and the
+ * rule, the outputs are unspecified and the next call is unaffected.  More than 16384 neighbours:
+ * PFX_ERR_CAPACITY.  raw (nullable): nq x S doubles, the matrix before normalisation, in out's
+ * index order; sums (nullable): nq doubles, the matrix sum as formed (0 where k <= 1 and no sum
+ * is taken).  Statistics of the last call: "spin_neighbors" (sum of k), "spin_kmax",
+ * "spin_too_few" / "spin_bad_cos" (rows that broke either rule), "spin_queued" (rows with more
+ * than "spin_cap_small" neighbours, which take the second pass); "spin_cap_small" and
+ * "spin_chunk" (neighbours per accumulation chunk) can be read from a new ctx. */
+pfx_status pfx_spin_image(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz,
+                          const float* snx, const float* sny, const float* snz, int64_t n_surface,
+                          const float* qx, const float* qy, const float* qz, const float* qnx,
+                          const float* qny, const float* qnz, int64_t nq, double radius,
+                          const pfx_spin_params* params, float* out, double* raw, double* sums);
+/* Device pointers, stream-ordered on the ctx stream, no host synchronisation: the errors above that
+ * follow the kernel, and the statistics, are reported by the next pfx_ctx_synchronize /
+ * pfx_ctx_last_stats on ctx. */
+pfx_status pfx_spin_image_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                              const float* d_snx, const float* d_sny, const float* d_snz,
+                              int64_t n_surface, const float* d_qx, const float* d_qy,
+                              const float* d_qz, const float* d_qnx, const float* d_qny,
+                              const float* d_qnz, int64_t nq, double radius,
+                              const pfx_spin_params* params, float* d_out, double* d_raw,
+                              double* d_sums);
 
 /* ---- range image + NARF keypoints ---------------------------------------------------- */
 /* out_points: width*height x 4 floats {x, y, z, range} (PointWithRange); unobserved pixels

@@ -9,6 +9,7 @@
 //   include/pcl_feature_extraction/tools.h:22-32        NormalEstimationOMP
 //   src/evaluation.cpp:593-612, :676-695, :766-785      FPFHEstimation, PFHEstimation, SHOTEstimationOMP
 //   src/evaluation.cpp:786-805                           SHOTColorEstimationOMP
+//   src/evaluation.cpp:514-553                           SpinImageEstimation, Histogram<153>
 //   src/evaluation.cpp:863-885, :257                     IterativeClosestPoint, transformPointCloud
 //   include/pcl_feature_extraction/features.h:224-273   KdTreeFLANN<FeatureT>::nearestKSearch,
 //                                                       Correspondence(s), boost::thread / ref
@@ -34,6 +35,7 @@
 #include <limits>
 #include <memory>
 #include <mutex>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
@@ -188,9 +190,21 @@ struct alignas(16) PointXYZI {
 };
 struct FPFHSignature33 { float histogram[33]; };
 struct PFHSignature125 { float histogram[125]; };
+// pcl::Histogram<N> (spin images, and later RIFT / intensity spin): N floats, nothing else
+template <int N>
+struct Histogram {
+  float histogram[N];
+  static int descriptorSize() { return N; }
+};
 struct SHOT352 { float descriptor[352]; float rf[9]; };
 struct SHOT1344 { float descriptor[1344]; float rf[9]; };
 struct ReferenceFrame { float x_axis[3], y_axis[3], z_axis[3]; };
+
+// pcl::PCLException, as far as the facade throws it (SpinImageEstimation where PCL's throws)
+class PCLException : public std::runtime_error {
+ public:
+  explicit PCLException(const std::string& what) : std::runtime_error(what) {}
+};
 
 template <typename T>
 class PointCloud {
@@ -474,6 +488,98 @@ class SHOTColorEstimationOMP : public FeatureFromNormals<PointInT, PointNT, Poin
       if (std::isnan(d[i * 1344])) out.is_dense = false;
     }
   }
+};
+
+// SpinImageEstimation<In, Normal, Histogram<153>> (evaluation.cpp:525).  As in PCL 1.7 it is not a
+// FeatureFromNormals: it keeps its own input normals, one per point of the *input* cloud, and the
+// normal of a point is the rotation axis of its image.  Custom rotation axes, the radial structure
+// and the angular domain are not on the accelerated path: compute() then fails with PCL_ERROR and
+// an empty output.  Where PCL's computeFeature throws (fewer neighbours than
+// setMinPointCountInNeighbourhood, a cosine out of range because an axis or normal is not of unit
+// length), compute() throws pcl::PCLException.
+template <typename PointInT, typename PointNT, typename PointOutT>
+class SpinImageEstimation : public Feature<PointInT, PointOutT> {
+ public:
+  typedef PointCloud<PointNT> PointCloudN;
+  typedef typename PointCloudN::Ptr PointCloudNPtr;
+  typedef typename PointCloudN::ConstPtr PointCloudNConstPtr;
+  typedef std::shared_ptr<SpinImageEstimation<PointInT, PointNT, PointOutT> > Ptr;
+  explicit SpinImageEstimation(unsigned int image_width = 8, double support_angle_cos = 0.0,
+                               unsigned int min_pts_neighb = 0)
+      : image_width_(image_width), support_angle_cos_(support_angle_cos), min_pts_neighb_(min_pts_neighb) {
+    this->name_ = "SpinImageEstimation";
+  }
+  void setInputNormals(const PointCloudNConstPtr& normals) { input_normals_ = normals; }
+  void setImageWidth(unsigned int bin_count) { image_width_ = bin_count; }
+  void setSupportAngle(double support_angle_cos) { support_angle_cos_ = support_angle_cos; }
+  void setMinPointCountInNeighbourhood(unsigned int min_pts_neighb) { min_pts_neighb_ = min_pts_neighb; }
+  void setRadialStructure(bool is_radial = true) { is_radial_ = is_radial; }
+  void setAngularDomain(bool is_angular = true) { is_angular_ = is_angular; }
+  void setRotationAxis(const PointNT& /*axis*/) { custom_axis_ = true; }
+  void setInputRotationAxes(const PointCloudNConstPtr& /*axes*/) { custom_axis_ = true; }
+  void useNormalsAsRotationAxis() { custom_axis_ = false; }
+
+ protected:
+  void computeFeature(PointCloud<PointOutT>& out) override {
+    const size_t nq = this->input_->size();
+    const int64_t S = ((int64_t)image_width_ + 1) * (2 * (int64_t)image_width_ + 1);
+    if (custom_axis_ || is_radial_ || is_angular_) {
+      PCL_ERROR("[pcl::SpinImageEstimation::compute] custom rotation axes, the radial structure and the "
+                "angular domain are not on the accelerated path\n");
+      return;
+    }
+    if (!input_normals_ || input_normals_->size() != nq) {
+      PCL_ERROR("[pcl::SpinImageEstimation::compute] the input normals are missing or do not match the input "
+                "cloud\n");
+      return;
+    }
+    if (image_width_ < 1 || image_width_ > 16 || S != (int64_t)(sizeof(PointOutT) / sizeof(float))) {
+      PCL_ERROR("[pcl::SpinImageEstimation::compute] (image_width + 1) * (2 * image_width + 1) = %lld does not "
+                "match the output histogram (image_width in [1, 16])\n", (long long)S);
+      return;
+    }
+    if (!(support_angle_cos_ >= 0.0 && support_angle_cos_ <= 1.0)) {
+      PCL_ERROR("[pcl::SpinImageEstimation::compute] the support angle cosine must be in [0, 1]\n");
+      return;
+    }
+    // PCL reads the normal of a *surface* neighbour from the input normals: meaningful only when
+    // the input cloud is the surface
+    const bool support = support_angle_cos_ > 0.0;
+    if (support && !this->input_is_surface()) {
+      PCL_ERROR("[pcl::SpinImageEstimation::compute] a support angle needs the input cloud to be the search "
+                "surface\n");
+      return;
+    }
+    const PointCloud<PointInT>& surf = this->surface();
+    const detail::SoA s = detail::soa_xyz(surf), q = detail::soa_xyz(*this->input_);
+    const detail::SoA ax = detail::soa_normals(*input_normals_);
+    pfx_spin_params prm;
+    pfx_spin_params_default(&prm);
+    prm.image_width = (int32_t)image_width_;
+    prm.support_angle_cos = support_angle_cos_;
+    prm.min_pts_neighb = (int32_t)min_pts_neighb_;
+    std::vector<float> h(nq * (size_t)S);
+    const pfx_status st = pfx_spin_image(
+        detail::context(), s.x.data(), s.y.data(), s.z.data(), support ? ax.x.data() : nullptr,
+        support ? ax.y.data() : nullptr, support ? ax.z.data() : nullptr, (int64_t)surf.size(), q.x.data(), q.y.data(),
+        q.z.data(), ax.x.data(), ax.y.data(), ax.z.data(), (int64_t)nq, this->search_radius_, &prm, h.data(), nullptr,
+        nullptr);
+    // (every argument was checked above: PFX_ERR_INVALID is one of the two rules PCL throws on)
+    if (st == PFX_ERR_INVALID)
+      throw PCLException(std::string("[pcl::SpinImageEstimation::compute] ") + pfx_last_error(detail::context()));
+    if (!detail::ok(st, "SpinImageEstimation")) return;
+    out.resize(nq);
+    out.is_dense = true;
+    for (size_t i = 0; i < nq; ++i) {
+      for (int64_t b = 0; b < S; ++b) out.points[i].histogram[b] = h[i * (size_t)S + (size_t)b];
+      if (std::isnan(h[i * (size_t)S])) out.is_dense = false;
+    }
+  }
+  PointCloudNConstPtr input_normals_;
+  unsigned int image_width_;
+  double support_angle_cos_;
+  unsigned int min_pts_neighb_;
+  bool is_radial_ = false, is_angular_ = false, custom_axis_ = false;
 };
 
 // ---- range image + NARF (keypoints.h:203-224) ---------------------------------------------
@@ -818,6 +924,7 @@ template <> struct DescriptorLayout<FPFHSignature33> { static constexpr int dim 
 template <> struct DescriptorLayout<SHOT352> { static constexpr int dim = 352, stride = 361; };
 template <> struct DescriptorLayout<SHOT1344> { static constexpr int dim = 1344, stride = 1353; };
 template <> struct DescriptorLayout<PFHSignature125> { static constexpr int dim = 125, stride = 125; };
+template <int N> struct DescriptorLayout<Histogram<N> > { static constexpr int dim = N, stride = N; };
 }  // namespace detail
 
 // KdTreeFLANN<FeatureT> with nearestKSearch(k = 1), as the reference uses it (features.h:258-272):

@@ -6,6 +6,6 @@ behind the C-ABI in include/pfx.h (libpfx.so).
 See DESIGN.md.
 """
 from ._native import PfxError, lib  # noqa: F401
-from .api import Batch, Context, IcpResult, camera, icp_params, narf_params  # noqa: F401
+from .api import Batch, Context, IcpResult, camera, icp_params, narf_params, spin_params  # noqa: F401
 
-__all__ = ["Batch", "Context", "IcpResult", "PfxError", "camera", "icp_params", "narf_params", "lib"]
+__all__ = ["Batch", "Context", "IcpResult", "PfxError", "camera", "icp_params", "narf_params", "spin_params", "lib"]

@@ -76,6 +76,17 @@ class IcpParams(ctypes.Structure):
     ]
 
 
+class SpinParams(ctypes.Structure):
+    """pfx_spin_params (SpinImageEstimation's constructor arguments and structure flags)."""
+    _fields_ = [
+        ("image_width", ctypes.c_int32),
+        ("support_angle_cos", ctypes.c_double),
+        ("min_pts_neighb", ctypes.c_int32),
+        ("radial", ctypes.c_int32),
+        ("angular", ctypes.c_int32),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "pfx_narf_params_default": (None, [ctypes.POINTER(NarfParams)]),
@@ -129,6 +140,11 @@ _SIGS = {
     "pfx_pfh": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl, c_vp]),
     "pfx_pfh_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
                             c_vp]),
+    "pfx_spin_params_default": (None, [ctypes.POINTER(SpinParams)]),
+    "pfx_spin_image": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                               c_i64, c_dbl, ctypes.POINTER(SpinParams), c_vp, c_vp, c_vp]),
+    "pfx_spin_image_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                   c_vp, c_i64, c_dbl, ctypes.POINTER(SpinParams), c_vp, c_vp, c_vp]),
     "pfx_range_image_planar": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(Camera), c_vp]),
     "pfx_narf_keypoints": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(Camera),
                                    ctypes.POINTER(NarfParams), c_vp, c_i64, c_i64p]),
@@ -182,8 +198,9 @@ _SIGS = {
 }
 
 # entry points an older library loaded through PFX_LIB (A/B runs against a previous build) may lack:
-# test hooks, and ICP (calling a missing one raises AttributeError there)
-_OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_icp_dev"}
+# test hooks, ICP and spin images (calling a missing one raises AttributeError there)
+_OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_icp_dev",
+                   "pfx_spin_params_default", "pfx_spin_image", "pfx_spin_image_dev"}
 
 _lib = None
 

@@ -56,6 +56,15 @@ def icp_params(**kw) -> N.IcpParams:
     return p
 
 
+def spin_params(image_width=8, support_angle_cos=0.0, min_pts_neighb=0, radial=0, angular=0) -> N.SpinParams:
+    """pfx_spin_params; the defaults are PCL's (pfx_spin_params_default)."""
+    p = N.SpinParams()
+    N.lib().pfx_spin_params_default(ctypes.byref(p))
+    p.image_width, p.support_angle_cos, p.min_pts_neighb = int(image_width), float(support_angle_cos), int(min_pts_neighb)
+    p.radial, p.angular = int(radial), int(angular)
+    return p
+
+
 #: result of Context.icp / icp_dev; state: 0 not converged, 1 iterations, 2 transform, 3 absolute
 #: MSE, 4 relative MSE, 5 no correspondences (pfx.h PFX_ICP_*); aligned: (x, y, z) or None
 IcpResult = collections.namedtuple("IcpResult",
@@ -233,6 +242,28 @@ class Context:
                                       _ptr(qx), _ptr(qy), _ptr(qz), nq, float(r), _ptr(out)))
         return out
 
+    def spin_image(self, sx, sy, sz, qx, qy, qz, qnx, qny, qnz, r, image_width=8, support_angle_cos=0.0,
+                   min_pts_neighb=0, surface_normals=None, debug=False, radial=0, angular=0):
+        """SpinImageEstimation (pfx_spin_image): (nq, (W + 1)(2W + 1)) float32; (qnx, qny, qnz) is the
+        rotation axis of each query (the input cloud's normal there).  surface_normals: (nx, ny, nz) of
+        the surface, needed when support_angle_cos > 0.  debug=True also returns raw (nq, S) float64,
+        the matrix before normalisation, and sums (nq,) float64."""
+        sx, sy, sz, qx, qy, qz, qnx, qny, qnz = map(_f32, (sx, sy, sz, qx, qy, qz, qnx, qny, qnz))
+        sn = (None, None, None) if surface_normals is None else tuple(map(_f32, surface_normals))
+        if len(qnx) != len(qx) or any(v is not None and len(v) != len(sx) for v in sn):
+            raise ValueError("spin_image: one axis per query and one normal per surface point")
+        nq = len(qx)
+        S = (int(image_width) + 1) * (2 * int(image_width) + 1) if 1 <= int(image_width) <= 16 else 1
+        out = np.empty((nq, S), dtype=np.float32)
+        raw = np.empty((nq, S), dtype=np.float64) if debug else None
+        sums = np.empty(nq, dtype=np.float64) if debug else None
+        p = spin_params(image_width, support_angle_cos, min_pts_neighb, radial, angular)
+        self._check(self._lib.pfx_spin_image(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(sn[0]), _ptr(sn[1]),
+                                             _ptr(sn[2]), len(sx), _ptr(qx), _ptr(qy), _ptr(qz), _ptr(qnx), _ptr(qny),
+                                             _ptr(qnz), nq, float(r), ctypes.byref(p), _ptr(out), _ptr(raw),
+                                             _ptr(sums)))
+        return (out, raw, sums) if debug else out
+
     def range_image_planar(self, x, y, z, cam=None):
         cam = cam or camera()
         x, y, z = map(_f32, (x, y, z))
@@ -391,6 +422,18 @@ class Context:
         self._check(self._lib.pfx_pfh_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(nx), _ptr(ny), _ptr(nz),
                                           sx.numel(), _ptr(qx), _ptr(qy), _ptr(qz), qx.numel(), float(r),
                                           _ptr(out)))
+
+    def spin_image_dev(self, sx, sy, sz, qx, qy, qz, qnx, qny, qnz, r, out, image_width=8, support_angle_cos=0.0,
+                       min_pts_neighb=0, surface_normals=None, raw=None, sums=None):
+        """pfx_spin_image_dev: out is an (nq, S) float32 device tensor, raw / sums optional float64
+        device tensors; no host synchronisation (too few neighbours, a cosine out of range or a
+        neighbourhood beyond capacity is reported by the next synchronize())."""
+        sn = (None, None, None) if surface_normals is None else tuple(surface_normals)
+        p = spin_params(image_width, support_angle_cos, min_pts_neighb)
+        self._check(self._lib.pfx_spin_image_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(sn[0]), _ptr(sn[1]),
+                                                 _ptr(sn[2]), sx.numel(), _ptr(qx), _ptr(qy), _ptr(qz), _ptr(qnx),
+                                                 _ptr(qny), _ptr(qnz), qx.numel(), float(r), ctypes.byref(p),
+                                                 _ptr(out), _ptr(raw), _ptr(sums)))
 
     def narf_keypoints_dev(self, x, y, z, params=None, cam=None, cap=1 << 20):
         cam = cam or camera()

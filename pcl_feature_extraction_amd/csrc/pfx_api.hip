@@ -107,6 +107,8 @@ pfx_status pfx_ctx_create(int device, pfx_ctx** out) {
     ctx->on_own_stream = true;  // created on first use (check_ctx)
     ctx->stats["pfh_cap_lds"] = pfx::pfh_cap_lds();
     ctx->stats["shot_color_cap_small"] = pfx::shot_color_cap_small();
+    ctx->stats["spin_cap_small"] = pfx::spin_cap_small();
+    ctx->stats["spin_chunk"] = pfx::spin_chunk();
     // grid builds by builder (pfx_grid.hip), and speculative counting builds that met a fat cell
     for (const char* s : {"grid_count_builds", "grid_sort_builds", "grid_hinted_sort_builds", "grid_fat_fallbacks"})
       ctx->stats[s] = 0;
@@ -140,6 +142,7 @@ void pfx_ctx_destroy(pfx_ctx* ctx) {
   if (ctx->host_scratch) (void)hipHostFree(ctx->host_scratch);
   if (ctx->fpfh_rb_mem) (void)hipHostFree(ctx->fpfh_rb_mem);
   if (ctx->pfh_rb_mem) (void)hipHostFree(ctx->pfh_rb_mem);
+  if (ctx->spin_rb_mem) (void)hipHostFree(ctx->spin_rb_mem);
   delete ctx;
 }
 
@@ -185,6 +188,7 @@ pfx_status pfx_ctx_trim(pfx_ctx* ctx) {
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   pfx::fpfh_resolve(ctx);
   pfx::pfh_resolve(ctx);
+  pfx::spin_resolve(ctx);
   pfx::narf_release(ctx);
   pfx::normals_release(ctx);
   pfx::keypoints_release(ctx);
@@ -206,6 +210,7 @@ pfx_status pfx_ctx_synchronize(pfx_ctx* ctx) {
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   pfx::fpfh_resolve(ctx);  // deferred statistics / capacity errors of the stream-ordered calls
   pfx::pfh_resolve(ctx);
+  pfx::spin_resolve(ctx);
   PFX_API_END(ctx)
 }
 
@@ -247,10 +252,11 @@ pfx_status pfx_ctx_kernel_time(pfx_ctx* ctx, const char* name, double* total_ms,
 pfx_status pfx_ctx_last_stats(pfx_ctx* ctx, const char* what, int64_t* value) {
   PFX_API_BEGIN
   if (!ctx || !what || !value) throw Error(PFX_ERR_INVALID, "null argument");
-  if (ctx->fpfh_pending || ctx->pfh_pending) {
+  if (ctx->fpfh_pending || ctx->pfh_pending || ctx->spin_pending) {
     PFX_HIP(hipStreamSynchronize(ctx->stream));
     pfx::fpfh_resolve(ctx);
     pfx::pfh_resolve(ctx);
+    pfx::spin_resolve(ctx);
   }
   auto it = ctx->stats.find(what);
   if (it == ctx->stats.end()) throw Error(PFX_ERR_INVALID, std::string("unknown stat ") + what);
@@ -665,6 +671,84 @@ pfx_status pfx_pfh(pfx_ctx* ctx, const float* sx, const float* sy, const float* 
   if (nq) PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * 125, hipMemcpyDeviceToHost, ctx->stream));
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   pfx::pfh_resolve(ctx);  // the host API reports at once
+  PFX_API_END(ctx)
+}
+
+void pfx_spin_params_default(pfx_spin_params* p) {
+  if (!p) return;
+  p->image_width = 8;
+  p->support_angle_cos = 0.0;
+  p->min_pts_neighb = 0;
+  p->radial = 0;
+  p->angular = 0;
+}
+
+// every check that precedes a launch (host and device entry points alike)
+static void spin_check(const float* sx, const float* sy, const float* sz, const float* snx, const float* sny,
+                       const float* snz, int64_t n_surface, const float* qx, const float* qy, const float* qz,
+                       const float* qnx, const float* qny, const float* qnz, int64_t nq, double radius,
+                       const pfx_spin_params* p, const float* out) {
+  if (!p || n_surface < 0 || nq < 0 || !(radius > 0.0) ||
+      (nq && (!out || !qx || !qy || !qz || !qnx || !qny || !qnz)) || (n_surface && (!sx || !sy || !sz)))
+    throw Error(PFX_ERR_INVALID, "spin_image: invalid arguments");
+  if (p->radial != 0 || p->angular != 0)
+    throw Error(PFX_ERR_UNSUPPORTED, "spin_image: the radial structure and the angular domain are not supported");
+  if (p->image_width < 1 || p->image_width > 16)
+    throw Error(PFX_ERR_INVALID, "spin_image: image_width must be in [1, 16]");
+  if (!(p->support_angle_cos >= 0.0 && p->support_angle_cos <= 1.0))
+    throw Error(PFX_ERR_INVALID, "spin_image: support_angle_cos must be in [0, 1]");
+  if (p->min_pts_neighb < 0) throw Error(PFX_ERR_INVALID, "spin_image: min_pts_neighb must be >= 0");
+  if (p->support_angle_cos > 0.0 && n_surface && (!snx || !sny || !snz))
+    throw Error(PFX_ERR_INVALID, "spin_image: a support angle needs the surface normals");
+}
+
+pfx_status pfx_spin_image_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                              const float* d_snx, const float* d_sny, const float* d_snz, int64_t n_surface,
+                              const float* d_qx, const float* d_qy, const float* d_qz, const float* d_qnx,
+                              const float* d_qny, const float* d_qnz, int64_t nq, double radius,
+                              const pfx_spin_params* params, float* d_out, double* d_raw, double* d_sums) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  spin_check(d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, d_qnx, d_qny, d_qnz, nq, radius,
+             params, d_out);
+  pfx::spin_dev(ctx, d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, d_qnx, d_qny, d_qnz, nq,
+                radius, *params, d_out, d_raw, d_sums);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_spin_image(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
+                          const float* sny, const float* snz, int64_t n_surface, const float* qx, const float* qy,
+                          const float* qz, const float* qnx, const float* qny, const float* qnz, int64_t nq,
+                          double radius, const pfx_spin_params* params, float* out, double* raw, double* sums) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  spin_check(sx, sy, sz, snx, sny, snz, n_surface, qx, qy, qz, qnx, qny, qnz, nq, radius, params, out);
+  const bool normals = params->support_angle_cos > 0.0 && n_surface;
+  const int64_t S = (int64_t)(params->image_width + 1) * (2 * params->image_width + 1);
+  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
+  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
+  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
+  float* dnx = normals ? stage_in(ctx, "in_nx", snx, n_surface) : nullptr;
+  float* dny = normals ? stage_in(ctx, "in_ny", sny, n_surface) : nullptr;
+  float* dnz = normals ? stage_in(ctx, "in_nz", snz, n_surface) : nullptr;
+  float* dqx = stage_in(ctx, "in_qx", qx, nq);
+  float* dqy = stage_in(ctx, "in_qy", qy, nq);
+  float* dqz = stage_in(ctx, "in_qz", qz, nq);
+  float* dax = stage_in(ctx, "in_qnx", qnx, nq);
+  float* day = stage_in(ctx, "in_qny", qny, nq);
+  float* daz = stage_in(ctx, "in_qnz", qnz, nq);
+  float* dout = ctx->buf("out_spin").as<float>(nq * S + 1);
+  double* draw = raw ? ctx->buf("out_spin_raw").as<double>(nq * S + 1) : nullptr;
+  double* dsums = sums ? ctx->buf("out_spin_sums").as<double>(nq + 1) : nullptr;
+  pfx::spin_dev(ctx, dsx, dsy, dsz, dnx, dny, dnz, n_surface, dqx, dqy, dqz, dax, day, daz, nq, radius, *params, dout,
+                draw, dsums);
+  if (nq) {
+    PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * S, hipMemcpyDeviceToHost, ctx->stream));
+    if (raw) PFX_HIP(hipMemcpyAsync(raw, draw, sizeof(double) * nq * S, hipMemcpyDeviceToHost, ctx->stream));
+    if (sums) PFX_HIP(hipMemcpyAsync(sums, dsums, sizeof(double) * nq, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  pfx::spin_resolve(ctx);  // the host API reports at once
   PFX_API_END(ctx)
 }
 

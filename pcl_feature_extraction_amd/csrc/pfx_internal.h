@@ -182,6 +182,9 @@ struct pfx_ctx {
   // pfh_dev's statistics / sticky error word, the same way (pfx::pfh_resolve)
   void* pfh_rb_mem = nullptr;
   bool pfh_pending = false;
+  // spin_dev's statistics / error words, the same way (pfx::spin_resolve)
+  void* spin_rb_mem = nullptr;
+  bool spin_pending = false;
   // one side stream + fork/join events (normal estimation's long-list chains), created on first use
   hipStream_t side = nullptr;
   hipEvent_t fork_ev[2] = {nullptr, nullptr};
@@ -361,6 +364,15 @@ void pfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, co
              const float* qz, int64_t nq, double r, float* out);
 void pfh_resolve(pfx_ctx* ctx);
 int pfh_cap_lds();  // neighbours a query's workgroup stages in LDS (stat "pfh_cap_lds")
+// spin images (pfx_spin.hip): stream-ordered, no host synchronisation; spin_resolve as pfh_resolve.
+// snx / sny / snz nullable unless prm.support_angle_cos > 0; raw / sums nullable
+void spin_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
+              const float* sny, const float* snz, int64_t ns, const float* qx, const float* qy,
+              const float* qz, const float* ax, const float* ay, const float* az, int64_t nq, double r,
+              const pfx_spin_params& prm, float* out, double* raw, double* sums);
+void spin_resolve(pfx_ctx* ctx);
+int spin_cap_small();  // neighbours of the first pass (stat "spin_cap_small")
+int spin_chunk();      // neighbours per accumulation chunk (stat "spin_chunk")
 void range_image_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
                      const pfx_camera& cam, float4* d_points);
 int64_t narf_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
