@@ -27,6 +27,11 @@
  *                          (features.h:175-196, evaluation.cpp:676-695)
  *   pfx_spin_image*     <- SpinImageEstimation<PointXYZRGB,Normal,Histogram<153>>::compute
  *                          (evaluation.cpp:514-553)
+ *   pfx_intensity_gradient* <- IntensityGradientEstimation<PointXYZI,Normal,IntensityGradient,
+ *                          IntensityFieldAccessor<PointXYZI>>::compute (evaluation.cpp:416-465;
+ *                          Tools::computeGradient, tools.h:40-54)
+ *   pfx_rift*           <- RIFTEstimation<PointXYZI,IntensityGradient,Histogram<32>>::compute
+ *                          (evaluation.cpp:716-765)
  *   pfx_range_image_planar* <- RangeImagePlanar::createFromPointCloudWithFixedSize
  *                          (keypoints.h:212-216, tools.h:61-77)
  *   pfx_narf_keypoints* <- RangeImageBorderExtractor + NarfKeypoint::compute
@@ -422,6 +427,65 @@ pfx_status pfx_spin_image_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy
                               const float* d_qnz, int64_t nq, double radius,
                               const pfx_spin_params* params, float* d_out, double* d_raw,
                               double* d_sums);
+
+/* ---- intensity gradients: IntensityGradientEstimation<PointXYZI, Normal, IntensityGradient,
+ *      IntensityFieldAccessor<PointXYZI>> (evaluation.cpp:416-465, tools.h:40-54) ------------- */
+/* out: nq x 3 floats.  si: the surface's intensities (pfx has no PointXYZI: PointXYZRGBtoXYZI's
+ * I = (0.299f r + 0.587f g) + 0.114f b is the caller's, Python's rgb_to_intensity).  Over the
+ * radius neighbours of query i in the surface, in FLANN order, all in float32: the centroid
+ * (sequential sums, times 1 / float(k)) and the mean intensity (sequential sum / float(k)); then,
+ * skipping a neighbour whose intensity is not finite, the six upper sums of A += p p^T and the
+ * three of b += p (I - mean) with p the neighbour minus the centroid; x = Eigen 3.2's
+ * A.colPivHouseholderQr().solve(b); the row is (Identity - n n^T) x with n = (qnx, qny, qnz)[i],
+ * the caller's, as for the spin-image axis.  No normalisation.  k < 3 (a non-finite query has
+ * k = 0): a NaN row.  A NaN normal, or a NaN intensity among the neighbours, gives a NaN row by
+ * that arithmetic.  Every NaN is written as 0x7fc00000.
+ * same_as_surface != 0: the queries are the surface itself (nq == n_surface; in the _dev form
+ * qx == sx, qy == sy, qz == sz), the case of Tools::computeGradient.  That call builds the normal
+ * estimation's neighbour lists and runs lane per list: its capacity is pfx_normals' and, like
+ * pfx_normals_dev, its _dev form reads the list sizes back inside the call.  Otherwise one
+ * workgroup serves a query, with at most 16384 neighbours (PFX_ERR_CAPACITY beyond, reported as
+ * the spin image's late errors are).  Both paths give the same bits for the same query.
+ * Null pointers, negative sizes, radius <= 0 or a same_as_surface call whose queries are not
+ * the surface: PFX_ERR_INVALID before any launch.  Statistics: "igrad_neighbors" (sum of k),
+ * "igrad_kmax". */
+pfx_status pfx_intensity_gradient(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz,
+                                  const float* si, int64_t n_surface, const float* qx, const float* qy,
+                                  const float* qz, const float* qnx, const float* qny, const float* qnz,
+                                  int64_t nq, int32_t same_as_surface, double radius, float* out);
+/* Device pointers, stream-ordered on the ctx stream; late errors and statistics as pfx_spin_image_dev. */
+pfx_status pfx_intensity_gradient_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                                      const float* d_si, int64_t n_surface, const float* d_qx,
+                                      const float* d_qy, const float* d_qz, const float* d_qnx,
+                                      const float* d_qny, const float* d_qnz, int64_t nq,
+                                      int32_t same_as_surface, double radius, float* d_out);
+
+/* ---- RIFT: RIFTEstimation<PointXYZI, IntensityGradient, Histogram<32>> (evaluation.cpp:716-765) */
+/* out: nq x D G floats, D = nr_distance_bins and G = nr_gradient_bins, each in [1, 16];
+ * out[gradient_bin D + distance_bin], PCL's histogram order.  (cx, cy, cz)[i] is the centre of
+ * row i; (sgx, sgy, sgz) are the surface's intensity gradients.  Every radius neighbour, in FLANN
+ * order, spreads its gradient magnitude bilinearly over its distance bins and (cyclically) its
+ * angle bins; the matrix is then scaled by 1 / sqrt(sum of squares), in Eigen 3.2's float
+ * summation order.  DESIGN.md "RIFT: the contract" states every operation; the CPU restatement
+ * of that text is the truth the kernel is tested against (parity with PCL itself is unpinned).
+ * The centre itself, when it is a neighbour, has no direction: angle 0.  A row whose gradients
+ * are all zero is NaN (0 x inf), as is a row with a NaN gradient in its ball.  No neighbour at
+ * all (a non-finite centre included): a NaN row, where PCL would leave the previous row's values.
+ * Every NaN is written as 0x7fc00000.  Null pointers, negative sizes, radius <= 0, D or G outside
+ * [1, 16]: PFX_ERR_INVALID before any launch.  More than 16384 neighbours: PFX_ERR_CAPACITY.
+ * Statistics: "rift_neighbors" (sum of k), "rift_kmax", "rift_queued" (rows with more than
+ * "rift_cap_small" neighbours, which take the second pass); "rift_cap_small" can be read from a
+ * new ctx. */
+pfx_status pfx_rift(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* sgx,
+                    const float* sgy, const float* sgz, int64_t n_surface, const float* cx, const float* cy,
+                    const float* cz, int64_t nq, double radius, int32_t nr_distance_bins,
+                    int32_t nr_gradient_bins, float* out);
+/* Device pointers, stream-ordered on the ctx stream, no host synchronisation; late errors and
+ * statistics as pfx_spin_image_dev. */
+pfx_status pfx_rift_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                        const float* d_sgx, const float* d_sgy, const float* d_sgz, int64_t n_surface,
+                        const float* d_cx, const float* d_cy, const float* d_cz, int64_t nq, double radius,
+                        int32_t nr_distance_bins, int32_t nr_gradient_bins, float* d_out);
 
 /* ---- range image + NARF keypoints ---------------------------------------------------- */
 /* out_points: width*height x 4 floats {x, y, z, range} (PointWithRange); unobserved pixels

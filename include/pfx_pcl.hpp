@@ -188,9 +188,19 @@ struct alignas(16) PointXYZI {
   float intensity = 0;
   float pad_[3] = {0, 0, 0};
 };
+// pcl::IntensityGradient: 16 bytes, the gradient as an array and by name
+struct alignas(16) IntensityGradient {
+  union {
+    float gradient[3];
+    struct { float gradient_x, gradient_y, gradient_z; };
+  };
+  float pad_ = 0;
+  IntensityGradient() : gradient{0, 0, 0} {}
+};
+static_assert(sizeof(IntensityGradient) == 16, "pcl::IntensityGradient is 16 bytes");
 struct FPFHSignature33 { float histogram[33]; };
 struct PFHSignature125 { float histogram[125]; };
-// pcl::Histogram<N> (spin images, and later RIFT / intensity spin): N floats, nothing else
+// pcl::Histogram<N> (spin images, RIFT, and later intensity spin): N floats, nothing else
 template <int N>
 struct Histogram {
   float histogram[N];
@@ -582,6 +592,149 @@ class SpinImageEstimation : public Feature<PointInT, PointOutT> {
   bool is_radial_ = false, is_angular_ = false, custom_axis_ = false;
 };
 
+// ---- intensity gradients and RIFT (evaluation.cpp:416-465, 716-765; tools.h:40-54) ------------
+namespace common {
+// common::IntensityFieldAccessor<PointXYZI> (common/intensity.h): the float accessor
+template <typename PointT> struct IntensityFieldAccessor;
+template <>
+struct IntensityFieldAccessor<PointXYZI> {
+  float operator()(const PointXYZI& p) const { return p.intensity; }
+  void get(const PointXYZI& p, float& intensity) const { intensity = p.intensity; }
+  void set(PointXYZI& p, float intensity) const { p.intensity = intensity; }
+  void demean(PointXYZI& p, float value) const { p.intensity -= value; }
+  void add(PointXYZI& p, float value) const { p.intensity += value; }
+};
+}  // namespace common
+
+// pcl::PointCloudXYZRGBtoXYZI (point_types_conversion.h): I = (0.299f r + 0.587f g) + 0.114f b
+inline void PointXYZRGBtoXYZI(const PointXYZRGB& in, PointXYZI& out) {
+  out.x = in.x; out.y = in.y; out.z = in.z;
+  const float r = (float)((in.rgba >> 16) & 255u), g = (float)((in.rgba >> 8) & 255u), b = (float)(in.rgba & 255u);
+  out.intensity = 0.299f * r + 0.587f * g + 0.114f * b;
+}
+inline void PointCloudXYZRGBtoXYZI(const PointCloud<PointXYZRGB>& in, PointCloud<PointXYZI>& out) {
+  out.points.resize(in.size());
+  out.width = in.width;
+  out.height = in.height;
+  out.is_dense = in.is_dense;
+  for (size_t i = 0; i < in.size(); ++i) PointXYZRGBtoXYZI(in.points[i], out.points[i]);
+}
+
+// IntensityGradientEstimation<PointXYZI, Normal, IntensityGradient, IntensityFieldAccessor<PointXYZI>>
+// with PCL 1.7's indexing: row i takes the neighbours of input point i in the surface, and the
+// normal normals_[i] -- the *surface's* i-th normal (the normals must match the surface, as PCL's
+// initCompute demands), so with keypoints as the input (evaluation.cpp:439-445) not the
+// keypoint's own.  Without a search surface (tools.h:50-53) the whole-cloud path runs.
+template <typename PointInT, typename PointNT, typename PointOutT,
+          typename IntensitySelectorT = common::IntensityFieldAccessor<PointInT> >
+class IntensityGradientEstimation : public FeatureFromNormals<PointInT, PointNT, PointOutT> {
+ public:
+  typedef std::shared_ptr<IntensityGradientEstimation<PointInT, PointNT, PointOutT, IntensitySelectorT> > Ptr;
+  IntensityGradientEstimation() { this->name_ = "IntensityGradientEstimation"; }
+  void setNumberOfThreads(unsigned int) {}
+
+ protected:
+  void computeFeature(PointCloud<PointOutT>& out) override {
+    const PointCloud<PointInT>& surf = this->surface();
+    const size_t nq = this->input_->size(), ns = surf.size();
+    if (!this->normals_ || this->normals_->size() != ns) {
+      PCL_ERROR("[pcl::IntensityGradientEstimation::compute] the input normals are missing or do not match the "
+                "search surface\n");
+      return;
+    }
+    if (nq > ns) {  // row i reads normals_[i]
+      PCL_ERROR("[pcl::IntensityGradientEstimation::compute] input index %zu is beyond the search surface "
+                "(%zu points)\n", ns, ns);
+      return;
+    }
+    const bool same = this->input_is_surface();
+    const detail::SoA s = detail::soa_xyz(surf), q = same ? detail::SoA() : detail::soa_xyz(*this->input_);
+    detail::SoA nrm = detail::soa_normals(*this->normals_);
+    nrm.x.resize(nq); nrm.y.resize(nq); nrm.z.resize(nq);
+    std::vector<float> si(ns), g(nq * 3);
+    IntensitySelectorT intensity;
+    for (size_t i = 0; i < ns; ++i) si[i] = intensity(surf.points[i]);
+    const detail::SoA& qq = same ? s : q;
+    if (!detail::ok(pfx_intensity_gradient(detail::context(), s.x.data(), s.y.data(), s.z.data(), si.data(),
+                                           (int64_t)ns, qq.x.data(), qq.y.data(), qq.z.data(), nrm.x.data(),
+                                           nrm.y.data(), nrm.z.data(), (int64_t)nq, same ? 1 : 0,
+                                           this->search_radius_, g.data()),
+                    "IntensityGradientEstimation"))
+      return;
+    out.resize(nq);
+    out.is_dense = true;
+    for (size_t i = 0; i < nq; ++i) {
+      for (int c = 0; c < 3; ++c) out.points[i].gradient[c] = g[3 * i + (size_t)c];
+      if (std::isnan(g[3 * i])) out.is_dense = false;
+    }
+  }
+};
+
+// RIFTEstimation<PointXYZI, IntensityGradient, Histogram<32>> with PCL 1.7's indexing:
+// `tree_->radiusSearch ((*indices_)[i], ...)` and `cloud.points[p_idx]` both index the search
+// *surface*, so row i describes surface_[i], not input point i (the input cloud only sets the number
+// of rows): those surface points are the centres passed to pfx_rift.  A caller who wants the
+// descriptor at the keypoints calls pfx_rift with them.  A row without neighbours is NaN (PCL
+// leaves the previous row's values).
+template <typename PointInT, typename GradientT, typename PointOutT>
+class RIFTEstimation : public Feature<PointInT, PointOutT> {
+ public:
+  typedef PointCloud<GradientT> PointCloudGradient;
+  typedef typename PointCloudGradient::Ptr PointCloudGradientPtr;
+  typedef typename PointCloudGradient::ConstPtr PointCloudGradientConstPtr;
+  typedef std::shared_ptr<RIFTEstimation<PointInT, GradientT, PointOutT> > Ptr;
+  RIFTEstimation() { this->name_ = "RIFTEstimation"; }
+  void setInputGradient(const PointCloudGradientConstPtr& gradient) { gradient_ = gradient; }
+  PointCloudGradientConstPtr getInputGradient() const { return gradient_; }
+  void setNrDistanceBins(int nr_distance_bins) { nr_distance_bins_ = nr_distance_bins; }
+  int getNrDistanceBins() const { return nr_distance_bins_; }
+  void setNrGradientBins(int nr_gradient_bins) { nr_gradient_bins_ = nr_gradient_bins; }
+  int getNrGradientBins() const { return nr_gradient_bins_; }
+
+ protected:
+  void computeFeature(PointCloud<PointOutT>& out) override {
+    const PointCloud<PointInT>& surf = this->surface();
+    const size_t nq = this->input_->size(), ns = surf.size();
+    const int D = nr_distance_bins_, G = nr_gradient_bins_;
+    if (!gradient_ || gradient_->size() != ns) {
+      PCL_ERROR("[pcl::RIFTEstimation::compute] the input gradient is missing or its size differs from the search "
+                "surface's\n");
+      return;
+    }
+    if (nq > ns) {  // row i reads surface_[i]
+      PCL_ERROR("[pcl::RIFTEstimation::compute] input index %zu is beyond the search surface (%zu points)\n", ns, ns);
+      return;
+    }
+    if (D < 1 || D > 16 || G < 1 || G > 16 || (size_t)(D * G) != sizeof(PointOutT) / sizeof(float)) {
+      PCL_ERROR("[pcl::RIFTEstimation::compute] nr_distance_bins * nr_gradient_bins = %d does not match the "
+                "output histogram (each in [1, 16])\n", D * G);
+      return;
+    }
+    const detail::SoA s = detail::soa_xyz(surf);
+    std::vector<float> gx(ns), gy(ns), gz(ns), h(nq * (size_t)(D * G));
+    for (size_t i = 0; i < ns; ++i) {
+      gx[i] = gradient_->points[i].gradient[0];
+      gy[i] = gradient_->points[i].gradient[1];
+      gz[i] = gradient_->points[i].gradient[2];
+    }
+    // (the centres are the first nq surface points: the arrays' own prefixes)
+    if (!detail::ok(pfx_rift(detail::context(), s.x.data(), s.y.data(), s.z.data(), gx.data(), gy.data(), gz.data(),
+                             (int64_t)ns, s.x.data(), s.y.data(), s.z.data(), (int64_t)nq, this->search_radius_, D, G,
+                             h.data()),
+                    "RIFTEstimation"))
+      return;
+    out.resize(nq);
+    out.is_dense = true;
+    const size_t S = (size_t)(D * G);
+    for (size_t i = 0; i < nq; ++i) {
+      for (size_t b = 0; b < S; ++b) out.points[i].histogram[b] = h[i * S + b];
+      if (std::isnan(h[i * S])) out.is_dense = false;
+    }
+  }
+  PointCloudGradientConstPtr gradient_;
+  int nr_distance_bins_ = 4, nr_gradient_bins_ = 4;
+};
+
 // ---- range image + NARF (keypoints.h:203-224) ---------------------------------------------
 class RangeImage : public PointCloud<PointWithRange> {
  public:
@@ -925,6 +1078,8 @@ template <> struct DescriptorLayout<SHOT352> { static constexpr int dim = 352, s
 template <> struct DescriptorLayout<SHOT1344> { static constexpr int dim = 1344, stride = 1353; };
 template <> struct DescriptorLayout<PFHSignature125> { static constexpr int dim = 125, stride = 125; };
 template <int N> struct DescriptorLayout<Histogram<N> > { static constexpr int dim = N, stride = N; };
+// (DefaultPointRepresentation<IntensityGradient>: the three gradient floats of a 16-byte point)
+template <> struct DescriptorLayout<IntensityGradient> { static constexpr int dim = 3, stride = 4; };
 }  // namespace detail
 
 // KdTreeFLANN<FeatureT> with nearestKSearch(k = 1), as the reference uses it (features.h:258-272):

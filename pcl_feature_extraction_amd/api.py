@@ -65,6 +65,16 @@ def spin_params(image_width=8, support_angle_cos=0.0, min_pts_neighb=0, radial=0
     return p
 
 
+def rgb_to_intensity(rgb) -> np.ndarray:
+    """pcl::PointXYZRGBtoXYZI on packed 0x00RRGGBB words: (0.299f * r + 0.587f * g) + 0.114f * b,
+    every step in float32.  Input preparation for Context.intensity_gradient, not a feature."""
+    c = _u32(rgb)
+    r = ((c >> 16) & 255).astype(np.float32)
+    g = ((c >> 8) & 255).astype(np.float32)
+    b = (c & 255).astype(np.float32)
+    return (np.float32(0.299) * r + np.float32(0.587) * g) + np.float32(0.114) * b
+
+
 #: result of Context.icp / icp_dev; state: 0 not converged, 1 iterations, 2 transform, 3 absolute
 #: MSE, 4 relative MSE, 5 no correspondences (pfx.h PFX_ICP_*); aligned: (x, y, z) or None
 IcpResult = collections.namedtuple("IcpResult",
@@ -264,6 +274,33 @@ class Context:
                                              _ptr(sums)))
         return (out, raw, sums) if debug else out
 
+    def intensity_gradient(self, sx, sy, sz, si, qx, qy, qz, qnx, qny, qnz, r, same_as_surface=False):
+        """IntensityGradientEstimation with the float intensity accessor (pfx_intensity_gradient):
+        (nq, 3) float32, NaN rows for queries with fewer than three neighbours.  si is the surface's
+        intensity (rgb_to_intensity), (qnx, qny, qnz) the normal at each query.  same_as_surface=True:
+        the queries are the surface (the whole-cloud path); the same bits either way."""
+        sx, sy, sz, si, qx, qy, qz, qnx, qny, qnz = map(_f32, (sx, sy, sz, si, qx, qy, qz, qnx, qny, qnz))
+        if len(si) != len(sx) or len(qnx) != len(qx):
+            raise ValueError("intensity_gradient: one intensity per surface point and one normal per query")
+        nq = len(qx)
+        out = np.empty((nq, 3), dtype=np.float32)
+        self._check(self._lib.pfx_intensity_gradient(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(si), len(sx),
+                                                     _ptr(qx), _ptr(qy), _ptr(qz), _ptr(qnx), _ptr(qny), _ptr(qnz),
+                                                     nq, 1 if same_as_surface else 0, float(r), _ptr(out)))
+        return out
+
+    def rift(self, sx, sy, sz, sgx, sgy, sgz, cx, cy, cz, r, nr_distance_bins=4, nr_gradient_bins=8):
+        """RIFTEstimation (pfx_rift): (nq, D G) float32, row[gradient_bin * D + distance_bin];
+        (sgx, sgy, sgz) are the surface's intensity gradients, (cx, cy, cz) the centres."""
+        sx, sy, sz, sgx, sgy, sgz, cx, cy, cz = map(_f32, (sx, sy, sz, sgx, sgy, sgz, cx, cy, cz))
+        if len(sgx) != len(sx):
+            raise ValueError("rift: one gradient per surface point")
+        nq, D, G = len(cx), int(nr_distance_bins), int(nr_gradient_bins)
+        out = np.empty((nq, D * G if 1 <= D <= 16 and 1 <= G <= 16 else 1), dtype=np.float32)
+        self._check(self._lib.pfx_rift(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(sgx), _ptr(sgy), _ptr(sgz), len(sx),
+                                       _ptr(cx), _ptr(cy), _ptr(cz), nq, float(r), D, G, _ptr(out)))
+        return out
+
     def range_image_planar(self, x, y, z, cam=None):
         cam = cam or camera()
         x, y, z = map(_f32, (x, y, z))
@@ -434,6 +471,23 @@ class Context:
                                                  _ptr(sn[2]), sx.numel(), _ptr(qx), _ptr(qy), _ptr(qz), _ptr(qnx),
                                                  _ptr(qny), _ptr(qnz), qx.numel(), float(r), ctypes.byref(p),
                                                  _ptr(out), _ptr(raw), _ptr(sums)))
+
+    def intensity_gradient_dev(self, sx, sy, sz, si, qx, qy, qz, qnx, qny, qnz, r, out, same_as_surface=False):
+        """pfx_intensity_gradient_dev: out is an (nq, 3) float32 device tensor.  same_as_surface=True
+        needs qx, qy, qz to be sx, sy, sz themselves and reads the list sizes back inside the call;
+        otherwise no host synchronisation (a neighbourhood beyond capacity is reported by the next
+        synchronize())."""
+        self._check(self._lib.pfx_intensity_gradient_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(si), sx.numel(),
+                                                         _ptr(qx), _ptr(qy), _ptr(qz), _ptr(qnx), _ptr(qny),
+                                                         _ptr(qnz), qx.numel(), 1 if same_as_surface else 0,
+                                                         float(r), _ptr(out)))
+
+    def rift_dev(self, sx, sy, sz, sgx, sgy, sgz, cx, cy, cz, r, out, nr_distance_bins=4, nr_gradient_bins=8):
+        """pfx_rift_dev: out is an (nq, D G) float32 device tensor; no host synchronisation (a
+        neighbourhood beyond capacity is reported by the next synchronize())."""
+        self._check(self._lib.pfx_rift_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(sgx), _ptr(sgy), _ptr(sgz),
+                                           sx.numel(), _ptr(cx), _ptr(cy), _ptr(cz), cx.numel(), float(r),
+                                           int(nr_distance_bins), int(nr_gradient_bins), _ptr(out)))
 
     def narf_keypoints_dev(self, x, y, z, params=None, cam=None, cap=1 << 20):
         cam = cam or camera()

@@ -109,6 +109,7 @@ pfx_status pfx_ctx_create(int device, pfx_ctx** out) {
     ctx->stats["shot_color_cap_small"] = pfx::shot_color_cap_small();
     ctx->stats["spin_cap_small"] = pfx::spin_cap_small();
     ctx->stats["spin_chunk"] = pfx::spin_chunk();
+    ctx->stats["rift_cap_small"] = pfx::rift_cap_small();
     // grid builds by builder (pfx_grid.hip), and speculative counting builds that met a fat cell
     for (const char* s : {"grid_count_builds", "grid_sort_builds", "grid_hinted_sort_builds", "grid_fat_fallbacks"})
       ctx->stats[s] = 0;
@@ -143,6 +144,7 @@ void pfx_ctx_destroy(pfx_ctx* ctx) {
   if (ctx->fpfh_rb_mem) (void)hipHostFree(ctx->fpfh_rb_mem);
   if (ctx->pfh_rb_mem) (void)hipHostFree(ctx->pfh_rb_mem);
   if (ctx->spin_rb_mem) (void)hipHostFree(ctx->spin_rb_mem);
+  if (ctx->rift_rb_mem) (void)hipHostFree(ctx->rift_rb_mem);
   delete ctx;
 }
 
@@ -189,6 +191,7 @@ pfx_status pfx_ctx_trim(pfx_ctx* ctx) {
   pfx::fpfh_resolve(ctx);
   pfx::pfh_resolve(ctx);
   pfx::spin_resolve(ctx);
+  pfx::rift_resolve(ctx);
   pfx::narf_release(ctx);
   pfx::normals_release(ctx);
   pfx::keypoints_release(ctx);
@@ -211,6 +214,7 @@ pfx_status pfx_ctx_synchronize(pfx_ctx* ctx) {
   pfx::fpfh_resolve(ctx);  // deferred statistics / capacity errors of the stream-ordered calls
   pfx::pfh_resolve(ctx);
   pfx::spin_resolve(ctx);
+  pfx::rift_resolve(ctx);
   PFX_API_END(ctx)
 }
 
@@ -252,11 +256,12 @@ pfx_status pfx_ctx_kernel_time(pfx_ctx* ctx, const char* name, double* total_ms,
 pfx_status pfx_ctx_last_stats(pfx_ctx* ctx, const char* what, int64_t* value) {
   PFX_API_BEGIN
   if (!ctx || !what || !value) throw Error(PFX_ERR_INVALID, "null argument");
-  if (ctx->fpfh_pending || ctx->pfh_pending || ctx->spin_pending) {
+  if (ctx->fpfh_pending || ctx->pfh_pending || ctx->spin_pending || ctx->igrad_pending || ctx->rift_pending) {
     PFX_HIP(hipStreamSynchronize(ctx->stream));
     pfx::fpfh_resolve(ctx);
     pfx::pfh_resolve(ctx);
     pfx::spin_resolve(ctx);
+    pfx::rift_resolve(ctx);
   }
   auto it = ctx->stats.find(what);
   if (it == ctx->stats.end()) throw Error(PFX_ERR_INVALID, std::string("unknown stat ") + what);
@@ -749,6 +754,105 @@ pfx_status pfx_spin_image(pfx_ctx* ctx, const float* sx, const float* sy, const 
   }
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   pfx::spin_resolve(ctx);  // the host API reports at once
+  PFX_API_END(ctx)
+}
+
+// every check that precedes a launch (host and device entry points alike)
+static void igrad_check(const float* sx, const float* sy, const float* sz, const float* si, int64_t n_surface,
+                        const float* qx, const float* qy, const float* qz, const float* qnx, const float* qny,
+                        const float* qnz, int64_t nq, int same, bool dev, double radius, const float* out) {
+  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!out || !qx || !qy || !qz || !qnx || !qny || !qnz)) ||
+      (n_surface && (!sx || !sy || !sz || !si)))
+    throw Error(PFX_ERR_INVALID, "intensity_gradient: invalid arguments");
+  if (same && (nq != n_surface || (dev && (qx != sx || qy != sy || qz != sz))))
+    throw Error(PFX_ERR_INVALID, "intensity_gradient: same_as_surface needs the queries to be the surface");
+}
+
+pfx_status pfx_intensity_gradient_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                                      const float* d_si, int64_t n_surface, const float* d_qx, const float* d_qy,
+                                      const float* d_qz, const float* d_qnx, const float* d_qny, const float* d_qnz,
+                                      int64_t nq, int32_t same_as_surface, double radius, float* d_out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  igrad_check(d_sx, d_sy, d_sz, d_si, n_surface, d_qx, d_qy, d_qz, d_qnx, d_qny, d_qnz, nq, same_as_surface, true,
+              radius, d_out);
+  pfx::igrad_dev(ctx, d_sx, d_sy, d_sz, d_si, n_surface, d_qx, d_qy, d_qz, d_qnx, d_qny, d_qnz, nq, same_as_surface,
+                 radius, d_out);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_intensity_gradient(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* si,
+                                  int64_t n_surface, const float* qx, const float* qy, const float* qz,
+                                  const float* qnx, const float* qny, const float* qnz, int64_t nq,
+                                  int32_t same_as_surface, double radius, float* out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  igrad_check(sx, sy, sz, si, n_surface, qx, qy, qz, qnx, qny, qnz, nq, same_as_surface, false, radius, out);
+  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
+  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
+  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
+  float* dsi = stage_in(ctx, "in_i", si, n_surface);
+  // (the whole-cloud path reads the surface's own arrays as its queries)
+  float* dqx = same_as_surface ? dsx : stage_in(ctx, "in_qx", qx, nq);
+  float* dqy = same_as_surface ? dsy : stage_in(ctx, "in_qy", qy, nq);
+  float* dqz = same_as_surface ? dsz : stage_in(ctx, "in_qz", qz, nq);
+  float* dnx = stage_in(ctx, "in_qnx", qnx, nq);
+  float* dny = stage_in(ctx, "in_qny", qny, nq);
+  float* dnz = stage_in(ctx, "in_qnz", qnz, nq);
+  float* dout = ctx->buf("out_igrad").as<float>(nq * 3 + 1);
+  pfx::igrad_dev(ctx, dsx, dsy, dsz, dsi, n_surface, dqx, dqy, dqz, dnx, dny, dnz, nq, same_as_surface, radius, dout);
+  if (nq) PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * 3, hipMemcpyDeviceToHost, ctx->stream));
+  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  pfx::rift_resolve(ctx);  // the host API reports at once
+  PFX_API_END(ctx)
+}
+
+static void rift_check(const float* sx, const float* sy, const float* sz, const float* sgx, const float* sgy,
+                       const float* sgz, int64_t n_surface, const float* cx, const float* cy, const float* cz,
+                       int64_t nq, double radius, int D, int G, const float* out) {
+  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!out || !cx || !cy || !cz)) ||
+      (n_surface && (!sx || !sy || !sz || !sgx || !sgy || !sgz)))
+    throw Error(PFX_ERR_INVALID, "rift: invalid arguments");
+  if (D < 1 || D > 16 || G < 1 || G > 16)
+    throw Error(PFX_ERR_INVALID, "rift: nr_distance_bins and nr_gradient_bins must be in [1, 16]");
+}
+
+pfx_status pfx_rift_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz, const float* d_sgx,
+                        const float* d_sgy, const float* d_sgz, int64_t n_surface, const float* d_cx,
+                        const float* d_cy, const float* d_cz, int64_t nq, double radius, int32_t nr_distance_bins,
+                        int32_t nr_gradient_bins, float* d_out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  rift_check(d_sx, d_sy, d_sz, d_sgx, d_sgy, d_sgz, n_surface, d_cx, d_cy, d_cz, nq, radius, nr_distance_bins,
+             nr_gradient_bins, d_out);
+  pfx::rift_dev(ctx, d_sx, d_sy, d_sz, d_sgx, d_sgy, d_sgz, n_surface, d_cx, d_cy, d_cz, nq, radius,
+                nr_distance_bins, nr_gradient_bins, d_out);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_rift(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* sgx,
+                    const float* sgy, const float* sgz, int64_t n_surface, const float* cx, const float* cy,
+                    const float* cz, int64_t nq, double radius, int32_t nr_distance_bins, int32_t nr_gradient_bins,
+                    float* out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  rift_check(sx, sy, sz, sgx, sgy, sgz, n_surface, cx, cy, cz, nq, radius, nr_distance_bins, nr_gradient_bins, out);
+  const int64_t S = (int64_t)nr_distance_bins * nr_gradient_bins;
+  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
+  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
+  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
+  float* dgx = stage_in(ctx, "in_nx", sgx, n_surface);
+  float* dgy = stage_in(ctx, "in_ny", sgy, n_surface);
+  float* dgz = stage_in(ctx, "in_nz", sgz, n_surface);
+  float* dcx = stage_in(ctx, "in_qx", cx, nq);
+  float* dcy = stage_in(ctx, "in_qy", cy, nq);
+  float* dcz = stage_in(ctx, "in_qz", cz, nq);
+  float* dout = ctx->buf("out_rift").as<float>(nq * S + 1);
+  pfx::rift_dev(ctx, dsx, dsy, dsz, dgx, dgy, dgz, n_surface, dcx, dcy, dcz, nq, radius, nr_distance_bins,
+                nr_gradient_bins, dout);
+  if (nq) PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * S, hipMemcpyDeviceToHost, ctx->stream));
+  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  pfx::rift_resolve(ctx);  // the host API reports at once
   PFX_API_END(ctx)
 }
 

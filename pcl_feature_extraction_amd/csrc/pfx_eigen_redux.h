@@ -53,4 +53,36 @@ PFX_HD double eigen_redux_sum(const double* m, int S) {
                             eigen_redux_lane(m, S, 3), m, S);
 }
 
+// ---- floats (SSE: packets of four, pfx_rift.hip and tests/cpp/rift_ref.cpp) ----
+//   S <  4: no packet: m[0], then the rest sequentially.
+//   S >= 4: packet_res0 = m[0..3]; when S >= 8 a second accumulator packet_res1 = m[4..7] and both
+//           advance by 8 up to 8 * (S / 8): eight running sums over the indices mod 8; then
+//           packet_res0 += packet_res1 lane-wise; then, when 4 * (S / 4) > 8 * (S / 8), the next
+//           packet is added lane-wise; predux = (a0 + a2) + (a1 + a3); the scalar tail is added
+//           left to right.
+PFX_HD float eigen_redux_sum_f(const float* m, int S) {
+  if (S <= 0) return 0.0f;
+  if (S < 4) {
+    float res = m[0];
+    for (int i = 1; i < S; ++i) res = res + m[i];
+    return res;
+  }
+  const int end4 = (S / 4) * 4, end8 = (S / 8) * 8;
+  float a[4] = {m[0], m[1], m[2], m[3]};
+  if (end8) {
+    float b[4] = {m[4], m[5], m[6], m[7]};
+    for (int i = 8; i < end8; i += 8)
+      for (int l = 0; l < 4; ++l) {
+        a[l] = a[l] + m[i + l];
+        b[l] = b[l] + m[i + 4 + l];
+      }
+    for (int l = 0; l < 4; ++l) a[l] = a[l] + b[l];
+    if (end4 > end8)
+      for (int l = 0; l < 4; ++l) a[l] = a[l] + m[end8 + l];
+  }
+  float res = (a[0] + a[2]) + (a[1] + a[3]);
+  for (int i = end4; i < S; ++i) res = res + m[i];
+  return res;
+}
+
 }  // namespace pfx

@@ -185,6 +185,9 @@ struct pfx_ctx {
   // spin_dev's statistics / error words, the same way (pfx::spin_resolve)
   void* spin_rb_mem = nullptr;
   bool spin_pending = false;
+  // igrad_dev's and rift_dev's, the same way (pfx::rift_resolve)
+  void* rift_rb_mem = nullptr;
+  bool igrad_pending = false, rift_pending = false;
   // one side stream + fork/join events (normal estimation's long-list chains), created on first use
   hipStream_t side = nullptr;
   hipEvent_t fork_ev[2] = {nullptr, nullptr};
@@ -373,6 +376,17 @@ void spin_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, c
 void spin_resolve(pfx_ctx* ctx);
 int spin_cap_small();  // neighbours of the first pass (stat "spin_cap_small")
 int spin_chunk();      // neighbours per accumulation chunk (stat "spin_chunk")
+// intensity gradients and RIFT (pfx_rift.hip): errors and statistics as spin images (rift_resolve
+// serves both).  igrad_dev with same != 0 (the queries are the surface) builds the normal
+// estimation's lists, with their host readback; the query path and rift_dev never wait.
+void igrad_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* si, int64_t ns,
+               const float* qx, const float* qy, const float* qz, const float* qnx, const float* qny,
+               const float* qnz, int64_t nq, int same, double r, float* out);
+void rift_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* sgx,
+              const float* sgy, const float* sgz, int64_t ns, const float* cx, const float* cy, const float* cz,
+              int64_t nq, double r, int D, int G, float* out);
+void rift_resolve(pfx_ctx* ctx);
+int rift_cap_small();  // neighbours of the first pass (stat "rift_cap_small")
 void range_image_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
                      const pfx_camera& cam, float4* d_points);
 int64_t narf_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
