@@ -301,7 +301,10 @@ pfx_status pfx_fpfh_prepare_dev(pfx_ctx* ctx, const float* d_sx, const float* d_
                                 int64_t n_surface, double radius);
 /* Also marks the SPFH point set S of the next pfx_fpfh_dev (input != surface) for these queries
  * (d_qx must be the same pointer, nq the same count): S needs only the coordinates, so it can be
- * found while the normals are still being computed.  Builds the surface grid first if needed. */
+ * found while the normals are still being computed.  Builds the surface grid first if needed.
+ * For up to 512 queries it also gathers and sorts every query's neighbours (the keypoint
+ * weighting's keys, 64 KiB of scratch per query), which that pfx_fpfh_dev then takes as they are;
+ * the query coordinates must not change in between. */
 pfx_status pfx_fpfh_prepare_queries_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
                                         int64_t n_surface, const float* d_qx, const float* d_qy,
                                         const float* d_qz, int64_t nq, double radius);

@@ -28,6 +28,13 @@ constexpr int kCapW = 8192;   // sorted-neighbour capacity of the weighting kern
 constexpr int64_t kCapWGlobal = 1 << 22;  // ... of its global-scratch pass (overflow queries)
 constexpr int kWOvfBlocks = 16;           // workgroups of that pass
 constexpr int kChunkW = 128;  // SPFH rows staged per chunk in the weighting kernel
+// ... when the keys were prepared ahead (k_fpfh_prep_keys): no sort scratch in LDS, so the row
+// buffers are kStageDepth times as long and the slowest query pays half as many chunk periods
+constexpr int kStageDepth = 2;
+constexpr int kChunkP = kStageDepth * kChunkW;
+// prepared keys: kCapW keys (64 KiB) per query for at most this many queries (32 MiB of scratch,
+// sized by the actual query count); more queries sort in the weighting kernel
+constexpr int64_t kPrepMaxQ = 512;
 constexpr int kWT = 1024;     // weighting workgroup: few queries, each as wide as possible
 constexpr int kHistCopies = 16;  // SPFH per-wave counter copies
 
@@ -162,6 +169,40 @@ __global__ void k_sorted_normals(const int32_t* __restrict__ perm, int64_t n, co
     return;
   }
   out[i] = make_float4(nx[p], ny[p], nz[p], 0.0f);
+}
+
+// The same copy for few queries: only the 5 x 5 x 5 cells around every query (cells are >= r, so
+// they hold its 2r ball, and FPFH reads no normal outside it: S lies within r of a query, the
+// SPFH pairs within r of S).  One workgroup per query and column of five cells, as
+// k_fpfh_mark_ball walks them; entries outside keep what an earlier call left there.
+__global__ void __launch_bounds__(256) k_sorted_normals_ball(GridView g, const float* __restrict__ qx,
+                                                             const float* __restrict__ qy,
+                                                             const float* __restrict__ qz, int64_t nq,
+                                                             const float* __restrict__ nx, const float* __restrict__ ny,
+                                                             const float* __restrict__ nz,
+                                                             const uint8_t* __restrict__ support,
+                                                             float4* __restrict__ out, int* __restrict__ zero9) {
+  if (zero9 && blockIdx.x == 0 && threadIdx.x < 9) zero9[threadIdx.x] = 0;
+  for (int64_t w = blockIdx.x; w < nq * 25; w += gridDim.x) {
+    const int64_t q = w / 25;
+    const int c = (int)(w - q * 25);
+    const float x = qx[q], y = qy[q], z = qz[q];
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) continue;
+    const int64_t cx = (int64_t)floor(((double)x - g.ox) * g.inv);
+    const int64_t cy = (int64_t)floor(((double)y - g.oy) * g.inv);
+    const int64_t cz = (int64_t)floor(((double)z - g.oz) * g.inv);
+    const int64_t z0 = max<int64_t>(cz - 2, 0), z1 = min<int64_t>(cz + 2, g.nz - 1);
+    const int64_t ix = cx + c / 5 - 2, iy = cy + c % 5 - 2;
+    if (z0 > z1 || ix < 0 || ix >= g.nx || iy < 0 || iy >= g.ny) continue;
+    const int64_t base = (ix * g.ny + iy) * g.nz;
+    const int32_t p0 = g.cell_start[base + z0], p1 = g.cell_start[base + z1 + 1];
+    for (int32_t i = p0 + threadIdx.x; i < p1; i += 256) {
+      const int32_t p = g.perm[i];
+      const bool in = !support || support[p];
+      const float nan = __builtin_nanf("");
+      out[i] = in ? make_float4(nx[p], ny[p], nz[p], 0.0f) : make_float4(nan, nan, nan, 0.0f);
+    }
+  }
 }
 
 // S membership by sorted position
@@ -427,6 +468,29 @@ __device__ __forceinline__ int lsb_exp_bound(float v) {
   return e == 255 ? 1000 : (e ? e : 1) - 150;
 }
 
+// The weighting's neighbour keys ahead of the normals: the gather and the bucketed sort of
+// k_fpfh_weight need the grid and the queries only, so fpfh_prepare_queries_dev runs them while
+// the normals are still being estimated.  Per query: its neighbour count (also when it exceeds
+// kCapW -- such a query goes to the global-scratch pass as before) and its sorted keys in a
+// kCapW-key slice of pkeys.
+__global__ void __launch_bounds__(kWT) k_fpfh_prep_keys(GridView g, const float* __restrict__ qx,
+                                                        const float* __restrict__ qy, const float* __restrict__ qz,
+                                                        int64_t nq, float rr, uint64_t* __restrict__ pkeys,
+                                                        int* __restrict__ pcount) {
+  extern __shared__ __attribute__((aligned(16))) uint64_t keys_lds[];  // kCapW keys + kCapW sort scratch
+  __shared__ BucketLdsT<kWT> SB;
+  __shared__ int s_count;
+  const int tid = threadIdx.x;
+  for (int64_t q = blockIdx.x; q < nq; q += gridDim.x) {
+    const int k = sorted_neighbors_bucketed<kWT>(g, qx[q], qy[q], qz[q], rr, keys_lds, keys_lds + kCapW, kCapW,
+                                                 &s_count, SB);
+    if (tid == 0) pcount[q] = k;
+    if (k <= kCapW)
+      for (int i = tid; i < k; i += kWT) pkeys[q * kCapW + i] = keys_lds[i];
+    __syncthreads();  // the keys are copied before the next query's gather overwrites them
+  }
+}
+
 // Weighting: one 1024-thread workgroup per query.  The 33 float chains (strict FLANN order)
 // run one per lane over SPFH rows staged in LDS.  The three double block sums are formed in
 // parallel: every value is a non-negative float, so when all of them are multiples of 2^L and
@@ -436,17 +500,25 @@ __device__ __forceinline__ int lsb_exp_bound(float v) {
 // GLOBAL = false: the sorted keys in LDS (kCapW); a query with more neighbours is pushed to
 // `ovf`.  GLOBAL = true: the overflow queries (count read on the device), keys in a
 // per-workgroup global scratch slice of gcap (PCL has no neighbour limit; kCapWGlobal here).
-template <bool GLOBAL>
+// PREP (GLOBAL = false only): count and sorted keys come from k_fpfh_prep_keys (pkeys / pcount,
+// the same gather and sort run ahead); the LDS holds kCapW keys and two row buffers of kChunkP
+// rows, staged by threads that keep one bin each (below).
+template <bool GLOBAL, bool PREP = false>
 __global__ void __launch_bounds__(kWT) k_fpfh_weight(GridView g, const float* __restrict__ qx,
                                                      const float* __restrict__ qy, const float* __restrict__ qz,
                                                      int64_t nq, float rr, const float* __restrict__ spfh,
                                                      float* __restrict__ out, int* __restrict__ err,
                                                      int32_t* __restrict__ ovf, int* __restrict__ n_ovf,
-                                                     uint64_t* __restrict__ scratch, int gcap) {
-  extern __shared__ __attribute__((aligned(16))) uint64_t keys_lds[];  // kCapW keys + kCapW sort scratch
+                                                     uint64_t* __restrict__ scratch, int gcap,
+                                                     const uint64_t* __restrict__ pkeys,
+                                                     const int* __restrict__ pcount) {
+  static_assert(!(GLOBAL && PREP), "prepared keys are the LDS pass's");
+  // kCapW keys, then kCapW keys of sort scratch (later two row buffers) / PREP: the two row buffers
+  extern __shared__ __attribute__((aligned(16))) uint64_t keys_lds[];
   __shared__ BucketLdsT<kWT> SB;
   uint64_t* keys = GLOBAL ? scratch + (size_t)blockIdx.x * gcap : keys_lds;
   const int kcap = GLOBAL ? gcap : kCapW;
+  constexpr int CH = PREP ? kChunkP : kChunkW;  // rows per staged chunk
   __shared__ float rows[kChunkW][kDesc + 1];
   __shared__ float wts[kChunkW];
   __shared__ double red_s[3][kWT / 64];
@@ -458,9 +530,24 @@ __global__ void __launch_bounds__(kWT) k_fpfh_weight(GridView g, const float* __
   for (int64_t w = blockIdx.x; w < count; w += gridDim.x) {
     const int64_t q = GLOBAL ? (int64_t)ovf[w] : w;
     // LDS: bucketed sort (a few barrier phases); global scratch: the bitonic network
-    const int k = GLOBAL ? sorted_neighbors(g, qx[q], qy[q], qz[q], rr, keys, kcap, &s_count)
-                         : sorted_neighbors_bucketed<kWT>(g, qx[q], qy[q], qz[q], rr, keys, keys + kCapW, kcap,
-                                                          &s_count, SB);
+    int k;
+    if constexpr (PREP) {
+      k = pcount[q];
+      if (k <= kCapW) {  // the sorted keys into LDS, every load in flight together
+        const uint64_t* pk = pkeys + q * kCapW;
+        uint64_t kv[kCapW / kWT];
+#pragma unroll
+        for (int u = 0; u < kCapW / kWT; ++u) kv[u] = pk[max(min(tid + u * kWT, k - 1), 0)];
+#pragma unroll
+        for (int u = 0; u < kCapW / kWT; ++u)
+          if (tid + u * kWT < k) keys[tid + u * kWT] = kv[u];
+        __syncthreads();
+      }
+    } else if constexpr (GLOBAL) {
+      k = sorted_neighbors(g, qx[q], qy[q], qz[q], rr, keys, kcap, &s_count);
+    } else {
+      k = sorted_neighbors_bucketed<kWT>(g, qx[q], qy[q], qz[q], rr, keys, keys + kCapW, kcap, &s_count, SB);
+    }
     if (k > kcap) {
       const bool give_up = GLOBAL || !ovf;
       if (tid == 0) {
@@ -483,24 +570,27 @@ __global__ void __launch_bounds__(kWT) k_fpfh_weight(GridView g, const float* __
     // rows of a chunk (+ its weights in column kDesc); LDS path: two buffers in the freed sort
     // scratch, so waves 1.. stage chunk c + 1 (and form chunk c's block partial sums) while wave 0
     // runs the 33 float chains over chunk c -- one barrier per chunk, the chains never wait for
-    // a gather.  Global-scratch path: one buffer, stage then chain.
+    // a gather.  Prepared keys: the same two buffers behind the keys, kChunkP rows each.
+    // Global-scratch path: one buffer, stage then chain.
     constexpr int RS = kDesc + 1;
     float* rb0 = GLOBAL ? &rows[0][0] : reinterpret_cast<float*>(keys_lds + kCapW);
-    float* rb1 = GLOBAL ? rb0 : rb0 + kChunkW * RS;
-    const int nch = (k + kChunkW - 1) / kChunkW;
-    auto stage = [&](int c, float* rbuf, int t0, int nt) {
-      const int c0 = c * kChunkW, m = min(kChunkW, k - c0), tot = m * kDesc;
-      // every row load first (clamped index: all issued back to back), then the LDS stores -- a
-      // load-then-store loop waited for each load in turn, one global latency per element a
-      // thread stages, on the critical path of the slowest query's chunk sequence
-      constexpr int PER = (kChunkW * kDesc + (kWT - 64) - 1) / (kWT - 64);
-      float v[PER];
+    float* rb1 = GLOBAL ? rb0 : rb0 + CH * RS;
+    const int nch = (k + CH - 1) / CH;
+    // every row load first (clamped index: all issued back to back), then the LDS stores -- a
+    // load-then-store loop waited for each load in turn, one global latency per element a
+    // thread stages, on the critical path of the slowest query's chunk sequence
+    constexpr int PER = (CH * kDesc + (kWT - 64) - 1) / (kWT - 64);
+    auto load = [&](int c, int t0, int nt, float (&v)[PER]) {
+      const int c0 = c * CH, tot = min(CH, k - c0) * kDesc;
 #pragma unroll
       for (int u = 0; u < PER; ++u) {
         const int e = min(t0 + u * nt, tot - 1);
         const int j = e / kDesc, b = e - j * kDesc;
         v[u] = spfh[(int64_t)key_idx(keys[c0 + j]) * kDesc + b];
       }
+    };
+    auto store = [&](int c, float* rbuf, int t0, int nt, const float (&v)[PER]) {
+      const int c0 = c * CH, m = min(CH, k - c0), tot = m * kDesc;
 #pragma unroll
       for (int u = 0; u < PER; ++u) {
         const int e = t0 + u * nt;
@@ -514,12 +604,56 @@ __global__ void __launch_bounds__(kWT) k_fpfh_weight(GridView g, const float* __
         rbuf[j * RS + kDesc] = d2 == 0.0f ? 0.0f : 1.0f / d2;  // 0 marks a skipped neighbour (d2 == 0)
       }
     };
+    auto stage = [&](int c, float* rbuf, int t0, int nt) {
+      float v[PER];
+      load(c, t0, nt, v);
+      store(c, rbuf, t0, nt, v);
+    };
     stage(0, rb0, tid, kWT);
+    // Prepared keys: a staging thread keeps one bin (fb) of every NR-th row (fr, fr + NR, ..), so
+    // neither its row gathers nor its share of the block partial sums divide by 33 or branch on
+    // the block -- the chunk period is the staging waves' instruction count, not a latency.  The
+    // rows are loaded two chunks ahead: chunk c + 2's loads are issued before chunk c's barrier
+    // and stored to LDS in the next period.
+    constexpr int NR = (kWT - 64) / kDesc, PERF = (CH + NR - 1) / NR;
+    const int ft = tid - 64;
+    const bool fon = PREP && ft >= 0 && ft < NR * kDesc;
+    const int fr = fon ? ft / kDesc : 0, fb = fon ? ft - fr * kDesc : 0;
+    auto loadf = [&](int c, float (&v)[PERF]) {
+      const int c0 = c * CH, m = min(CH, k - c0);
+#pragma unroll
+      for (int u = 0; u < PERF; ++u) v[u] = spfh[(int64_t)key_idx(keys[c0 + min(fr + u * NR, m - 1)]) * kDesc + fb];
+    };
+    auto storef = [&](int c, float* rbuf, const float (&v)[PERF]) {
+      const int c0 = c * CH, m = min(CH, k - c0);
+      if (fon) {
+#pragma unroll
+        for (int u = 0; u < PERF; ++u)
+          if (fr + u * NR < m) rbuf[(fr + u * NR) * RS + fb] = v[u];
+      }
+      for (int j = ft; j < m; j += kWT - 64) {
+        const float d2 = key_d2(keys[c0 + j]);
+        rbuf[j * RS + kDesc] = d2 == 0.0f ? 0.0f : 1.0f / d2;
+      }
+    };
+    float pv[PERF];
+    double fps = 0.0;
+    int fpl = 1 << 20;
+    if constexpr (PREP) {
+      if (tid >= 64 && nch > 1) loadf(1, pv);
+    }
     __syncthreads();
     for (int c = 0; c < nch; ++c) {
-      const int c0 = c * kChunkW, m = min(kChunkW, k - c0);
+      const int c0 = c * CH, m = min(CH, k - c0);
       const float* cur = (c & 1) ? rb1 : rb0;
-      if (!GLOBAL && tid >= 64 && c + 1 < nch) stage(c + 1, (c & 1) ? rb0 : rb1, tid - 64, kWT - 64);
+      if constexpr (PREP) {
+        if (tid >= 64 && c + 1 < nch) {
+          storef(c + 1, (c & 1) ? rb0 : rb1, pv);
+          if (c + 2 < nch) loadf(c + 2, pv);
+        }
+      } else if (!GLOBAL && tid >= 64 && c + 1 < nch) {
+        stage(c + 1, (c & 1) ? rb0 : rb1, tid - 64, kWT - 64);
+      }
       if (tid < kDesc) {
         // skipped neighbours have w = 0: SPFH rows are finite and fh >= +0, so adding the +0
         // product leaves fh unchanged bit for bit (== PCL's `continue`)
@@ -527,7 +661,16 @@ __global__ void __launch_bounds__(kWT) k_fpfh_weight(GridView g, const float* __
         for (int j = 0; j < m; ++j) fh = fh + cur[j * RS + tid] * cur[j * RS + kDesc];
       }
       const int pt0 = GLOBAL ? tid : tid - 64, pnt = GLOBAL ? kWT : kWT - 64;
-      if (pt0 >= 0) {
+      if constexpr (PREP) {
+        if (fon) {
+          for (int j = fr; j < m; j += NR) {
+            const float w = cur[j * RS + kDesc];
+            const float v = w == 0.0f ? 0.0f : cur[j * RS + fb] * w;
+            fps += (double)v;  // +0 for a skipped neighbour or an empty bin: the sum is unchanged
+            fpl = v != 0.0f ? min(fpl, lsb_exp(v)) : fpl;
+          }
+        }
+      } else if (pt0 >= 0) {
         for (int e = pt0; e < m * kDesc; e += pnt) {
           const int j = e / kDesc, b = e - j * kDesc;
           const float w = cur[j * RS + kDesc];
@@ -546,6 +689,11 @@ __global__ void __launch_bounds__(kWT) k_fpfh_weight(GridView g, const float* __
         stage(c + 1, rb0, tid, kWT);
         __syncthreads();
       }
+    }
+    if (fon) {  // the thread's bin lies in one block
+      if (fb < kBins) { ps0 = fps; pl0 = fpl; }
+      else if (fb < 2 * kBins) { ps1 = fps; pl1 = fpl; }
+      else { ps2 = fps; pl2 = fpl; }
     }
     // block reduction (any order: only used when every partial sum is exact)
 #pragma unroll
@@ -916,6 +1064,16 @@ void fpfh_prepare_queries_dev(pfx_ctx* ctx, const float* sx, const float* sy, co
   check_launch("k_fpfh_mark");
   PFX_HIP(rocprim::select(tmp, tmp_bytes, rocprim::counting_iterator<int32_t>(0), flags, slist, d_sel, (size_t)ns,
                           st));
+  // the weighting's sorted keys (scratch bounded: kPrepMaxQ queries of kCapW keys)
+  ctx->prep_keys = nq <= kPrepMaxQ;
+  if (ctx->prep_keys) {
+    uint64_t* pkeys = ctx->buf("fpfh_pkeys").as<uint64_t>((size_t)nq * kCapW);
+    int* pcount = ctx->buf("fpfh_pcount").as<int>(nq);
+    const size_t lds = sizeof(uint64_t) * 2 * kCapW;
+    PFX_HIP(hipFuncSetAttribute((const void*)k_fpfh_prep_keys, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    k_fpfh_prep_keys<<<(unsigned)nq, kWT, lds, st>>>(view(G), qx, qy, qz, nq, (float)(r * r), pkeys, pcount);
+    check_launch("k_fpfh_prep_keys");
+  }
   ctx->prep_qx = qx;
   ctx->prep_nq = nq;
 }
@@ -987,10 +1145,13 @@ void fpfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, c
   const bool rebuilt = grid_ready && fpfh_validate_grid(ctx);
   // S marked ahead (fpfh_prepare_queries_dev on this grid and these queries)?
   const bool s_ready = grid_ready && !rebuilt && !same && ctx->prep_qx == qx && ctx->prep_nq == nq;
+  // ... with the weighting's sorted keys (k_fpfh_prep_keys on the same grid and queries)?
+  const bool k_ready = s_ready && ctx->prep_keys;
   ctx->prep_x = nullptr;  // one-shot
   ctx->prep_n = -1;
   ctx->prep_qx = nullptr;
   ctx->prep_nq = -1;
+  ctx->prep_keys = false;
   const Grid& G = ctx->grid_b;
   GridView g = view(G);
   const float rr = (float)(r * r);
@@ -1014,8 +1175,14 @@ void fpfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, c
     TimeScope ts(ctx, "fpfh_mark");
     // (also zeroes the per-call statistics words err[1..9]: err[0] (neighbourhood beyond
     // capacity) is sticky until the check after the next synchronisation, fpfh_resolve)
-    k_sorted_normals<<<nb, 256, 0, st>>>(G.perm, ns, snx, sny, snz, same ? nullptr : ctx->fpfh_support, snp,
-                                         err + 1);
+    // few queries on a large surface: only the cells FPFH can read (threshold not swept: a query's
+    // 125 cells hold up to ~2^14 points of the 1M-point room, and the copy must stay below ns)
+    if (!same && nq * 4096 <= ns)
+      k_sorted_normals_ball<<<(unsigned)(nq * 25), 256, 0, st>>>(g, qx, qy, qz, nq, snx, sny, snz, ctx->fpfh_support,
+                                                                 snp, err + 1);
+    else
+      k_sorted_normals<<<nb, 256, 0, st>>>(G.perm, ns, snx, sny, snz, same ? nullptr : ctx->fpfh_support, snp,
+                                           err + 1);
     ctx->fpfh_support = nullptr;  // one-shot
     if (!s_ready) {
       if (same) {
@@ -1086,13 +1253,25 @@ void fpfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, c
     check_launch("k_fpfh_weight_lists");
   } else {
     TimeScope ts(ctx, "fpfh_weight", true);
-    const size_t lds = sizeof(uint64_t) * 2 * kCapW;
-    PFX_HIP(hipFuncSetAttribute((const void*)k_fpfh_weight<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const unsigned blocks = (unsigned)std::min<int64_t>(nq, PFX_W_BLOCKS);
-    k_fpfh_weight<false><<<blocks, kWT, lds, st>>>(g, qx, qy, qz, nq, rr, spfh, out, err, ovf, err + 8, nullptr, 0);
+    ctx->stats["fpfh_weight_prepared"] = k_ready ? 1 : 0;
+    if (k_ready) {  // keys sorted ahead: kCapW keys and two row buffers of kChunkP rows in LDS
+      const size_t lds = sizeof(uint64_t) * kCapW + sizeof(float) * 2 * kChunkP * (kDesc + 1);
+      PFX_HIP(hipFuncSetAttribute((const void*)k_fpfh_weight<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds));
+      k_fpfh_weight<false, true><<<blocks, kWT, lds, st>>>(g, qx, qy, qz, nq, rr, spfh, out, err, ovf, err + 8, nullptr,
+                                                           0, ctx->buf("fpfh_pkeys").as<uint64_t>((size_t)nq * kCapW),
+                                                           ctx->buf("fpfh_pcount").as<int>(nq));
+    } else {
+      const size_t lds = sizeof(uint64_t) * 2 * kCapW;
+      PFX_HIP(hipFuncSetAttribute((const void*)k_fpfh_weight<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds));
+      k_fpfh_weight<false><<<blocks, kWT, lds, st>>>(g, qx, qy, qz, nq, rr, spfh, out, err, ovf, err + 8, nullptr, 0,
+                                                     nullptr, nullptr);
+    }
     if (overflow_pass)
       k_fpfh_weight<true><<<kWOvfBlocks, kWT, 0, st>>>(g, qx, qy, qz, nq, rr, spfh, out, err, ovf, err + 8, wscratch,
-                                                        gcap);
+                                                        gcap, nullptr, nullptr);
     check_launch("k_fpfh_weight");
   }
   // statistics and the sticky error word land in pinned memory in stream order; no host

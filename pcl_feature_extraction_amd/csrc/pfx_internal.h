@@ -158,6 +158,7 @@ struct pfx_ctx {
   // ... and its SPFH point set for these queries (pfx_fpfh_prepare_queries_dev)
   const float* prep_qx = nullptr;
   int64_t prep_nq = -1;
+  bool prep_keys = false;  // ... with the weighting's sorted keys of every query (set with prep_qx)
   const uint8_t* fpfh_support = nullptr;  // pfx_fpfh_support_mask_dev -> next pfx_fpfh_dev
   // a speculative grid_b (pfx_fpfh_prepare_dev on the previous scan's widened bounds): its
   // out-of-bounds count, copied to pinned memory in stream order, checked by the first consumer
