@@ -32,6 +32,10 @@
  *                          Tools::computeGradient, tools.h:40-54)
  *   pfx_rift*           <- RIFTEstimation<PointXYZI,IntensityGradient,Histogram<32>>::compute
  *                          (evaluation.cpp:716-765)
+ *   pfx_shape_context*  <- ShapeContext3DEstimation<PointXYZRGB,Normal,ShapeContext1980>::compute
+ *                          (features.h:175-196, evaluation.cpp:319-345)
+ *   pfx_usc*            <- UniqueShapeContext<PointXYZRGB,ShapeContext1980>::compute
+ *                          (evaluation.cpp:346-371); pfx_shot_lrf* its frames
  *   pfx_range_image_planar* <- RangeImagePlanar::createFromPointCloudWithFixedSize
  *                          (keypoints.h:212-216, tools.h:61-77)
  *   pfx_narf_keypoints* <- RangeImageBorderExtractor + NarfKeypoint::compute
@@ -489,6 +493,63 @@ pfx_status pfx_rift_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, cons
                         const float* d_sgx, const float* d_sgy, const float* d_sgz, int64_t n_surface,
                         const float* d_cx, const float* d_cy, const float* d_cz, int64_t nq, double radius,
                         int32_t nr_distance_bins, int32_t nr_gradient_bins, float* d_out);
+
+/* ---- 3D shape contexts: ShapeContext3DEstimation<PointXYZRGB, Normal, ShapeContext1980>
+ * (evaluation.cpp:319-345) and UniqueShapeContext<PointXYZRGB, ShapeContext1980> (:346-371) ---- */
+/* desc: nq x 1980 floats, bin = azimuth * 165 + elevation * 15 + radial (12 x 11 x 15, PCL 1.7's
+ * fixed bins); rf: nq x 9 floats (x, y, z axis).  Every radius neighbour of a query (FLANN order,
+ * strict d^2 < (float)(radius^2)) that is not within the close-point skip (|d^2| < FLT_EPSILON)
+ * adds (1 / density) * lut[bin] to its bin, a float addition in neighbour order; density is the
+ * number of surface points with d^2 < (float)(point_density_radius^2) around that neighbour,
+ * itself included.  DESIGN.md "Shape contexts: the contract" states every operation; the CPU
+ * restatement of that text is the truth the kernels are tested against (parity with PCL itself is
+ * unpinned).
+ * pfx_shape_context: the z axis of a row is the surface normal of its nearest neighbour; its x axis
+ * is made from three floats of a random stream, orthogonalised against the normal.  rnd == NULL:
+ * the stream of boost::mt19937 seeded 12345 through uniform_01<float>, from its start; else rnd
+ * holds 3 nq floats and the t-th drawing row takes rnd[3t .. 3t + 2].  A row draws when its query
+ * is finite and has a neighbour; a row that does not is NaN with a zero rf.  A NaN normal gives
+ * NaN x and y axes and a finite row.
+ * pfx_usc: the frame of row i is frames[9 i ..] (x, y, z axis; pfx_shot_lrf's layout): x its x
+ * axis, the normal its z axis, rf a copy.  A non-finite query, or a frame whose x, y or z axis has
+ * a non-finite first component: a NaN row with a zero rf.  No neighbour: a zero row.
+ * Every NaN is written as 0x7fc00000.  Null pointers (rnd excepted), negative sizes, any radius
+ * <= 0 or radius < min_radius: PFX_ERR_INVALID before any launch.  More than 16384 neighbours:
+ * PFX_ERR_CAPACITY.  Statistics: "sc_neighbors" (sum of k), "sc_kmax", "sc_draws" (drawing rows),
+ * "sc_skipped_close", "sc_support" (surface points whose density was counted: those in the ball of
+ * a finite query), "sc_queued" (rows with more than "sc_cap_small" neighbours, which take the
+ * second pass); "sc_cap_small" can be read from a new ctx. */
+pfx_status pfx_shape_context(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
+                             const float* sny, const float* snz, int64_t n_surface, const float* qx,
+                             const float* qy, const float* qz, int64_t nq, double radius, double min_radius,
+                             double point_density_radius, const float* rnd, float* desc, float* rf);
+pfx_status pfx_usc(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t n_surface,
+                   const float* qx, const float* qy, const float* qz, const float* frames, int64_t nq,
+                   double radius, double min_radius, double point_density_radius, float* desc, float* rf);
+/* SHOTLocalReferenceFrameEstimation alone: rf (nq x 9) equals pfx_shot's rf at the same radius bit
+ * for bit, NaN rows (a non-finite query, fewer than five valid neighbours) and capacity (16384
+ * neighbours, PFX_ERR_CAPACITY beyond) included. */
+pfx_status pfx_shot_lrf(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t n_surface,
+                        const float* qx, const float* qy, const float* qz, int64_t nq, double radius, float* rf);
+/* Device pointers, stream-ordered on the ctx stream (the surface grid's bounds are read back when
+ * it was not prepared ahead, as for pfx_spin_image_dev; the first pfx_shape_context_dev call
+ * without rnd uploads the default stream); late errors and statistics as pfx_spin_image_dev. */
+pfx_status pfx_shape_context_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                                 const float* d_snx, const float* d_sny, const float* d_snz, int64_t n_surface,
+                                 const float* d_qx, const float* d_qy, const float* d_qz, int64_t nq,
+                                 double radius, double min_radius, double point_density_radius,
+                                 const float* d_rnd, float* d_desc, float* d_rf);
+pfx_status pfx_usc_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz, int64_t n_surface,
+                       const float* d_qx, const float* d_qy, const float* d_qz, const float* d_frames, int64_t nq,
+                       double radius, double min_radius, double point_density_radius, float* d_desc,
+                       float* d_rf);
+pfx_status pfx_shot_lrf_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                            int64_t n_surface, const float* d_qx, const float* d_qy, const float* d_qz, int64_t nq,
+                            double radius, float* d_rf);
+/* Host only: n floats of the stream of boost::mt19937 seeded `seed` (init_genrand) read through
+ * uniform_01<float> (v = (float)u32 / 2^32, drawn again unless v < 1), after skipping `skip`
+ * floats. */
+pfx_status pfx_rng_uniform01(uint32_t seed, int64_t skip, int64_t n, float* out);
 
 /* ---- range image + NARF keypoints ---------------------------------------------------- */
 /* out_points: width*height x 4 floats {x, y, z, range} (PointWithRange); unobserved pixels

@@ -32,6 +32,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <ctime>
 #include <limits>
 #include <memory>
 #include <mutex>
@@ -208,6 +209,7 @@ struct Histogram {
 };
 struct SHOT352 { float descriptor[352]; float rf[9]; };
 struct SHOT1344 { float descriptor[1344]; float rf[9]; };
+struct ShapeContext1980 { float descriptor[1980]; float rf[9]; };
 struct ReferenceFrame { float x_axis[3], y_axis[3], z_axis[3]; };
 
 // pcl::PCLException, as far as the facade throws it (SpinImageEstimation where PCL's throws)
@@ -735,6 +737,179 @@ class RIFTEstimation : public Feature<PointInT, PointOutT> {
   int nr_distance_bins_ = 4, nr_gradient_bins_ = 4;
 };
 
+// ---- 3D shape contexts (evaluation.cpp:319-371) ------------------------------------------------
+namespace detail {
+template <typename PointOutT>
+inline void sc_rows(const std::vector<float>& d, const std::vector<float>& rf, size_t nq, PointCloud<PointOutT>& out) {
+  static_assert(sizeof(PointOutT) == sizeof(float) * (1980 + 9), "a ShapeContext1980 output");
+  out.resize(nq);
+  out.is_dense = true;
+  for (size_t i = 0; i < nq; ++i) {
+    for (int b = 0; b < 1980; ++b) out.points[i].descriptor[b] = d[i * 1980 + b];
+    for (int b = 0; b < 9; ++b) out.points[i].rf[b] = rf[i * 9 + b];
+    if (std::isnan(d[i * 1980])) out.is_dense = false;
+  }
+}
+// PCL's initCompute rule of both shape contexts
+inline bool sc_radii_ok(const char* who, double radius, double min_radius, double density_radius) {
+  if (radius < min_radius || !(min_radius > 0.0) || !(density_radius > 0.0)) {
+    PCL_ERROR("[pcl::%s::compute] the search radius (%g) must not be below the minimal radius (%g), and the minimal "
+              "and point density (%g) radii must be positive\n", who, radius, min_radius, density_radius);
+    return false;
+  }
+  return true;
+}
+}  // namespace detail
+
+// ShapeContext3DEstimation<In, Normal, ShapeContext1980>: PCL 1.7's fixed 12 x 11 x 15 bins.  The
+// estimator owns its random stream (boost::mt19937 seeded 12345, or from the clock with
+// random = true) and never reseeds it: a second compute() continues where the first one stopped,
+// three floats per row that has a neighbour.
+template <typename PointInT, typename PointNT, typename PointOutT = ShapeContext1980>
+class ShapeContext3DEstimation : public FeatureFromNormals<PointInT, PointNT, PointOutT> {
+ public:
+  typedef std::shared_ptr<ShapeContext3DEstimation<PointInT, PointNT, PointOutT> > Ptr;
+  explicit ShapeContext3DEstimation(bool random = false)
+      : seed_(random ? static_cast<uint32_t>(std::time(nullptr)) : 12345u) {
+    this->name_ = "ShapeContext3DEstimation";
+  }
+  void setMinimalRadius(double radius) { min_radius_ = radius; }
+  double getMinimalRadius() const { return min_radius_; }
+  void setPointDensityRadius(double radius) { point_density_radius_ = radius; }
+  double getPointDensityRadius() const { return point_density_radius_; }
+  size_t getAzimuthBins() const { return 12; }
+  size_t getElevationBins() const { return 11; }
+  size_t getRadiusBins() const { return 15; }
+
+ protected:
+  void computeFeature(PointCloud<PointOutT>& out) override {
+    const PointCloud<PointInT>& surf = this->surface();
+    if (!detail::sc_radii_ok("ShapeContext3DEstimation", this->search_radius_, min_radius_, point_density_radius_))
+      return;
+    if (!this->normals_ || this->normals_->size() != surf.size()) {
+      PCL_ERROR("[pcl::ShapeContext3DEstimation::compute] the normals are missing or their number (%zu) differs from "
+                "the search surface's points (%zu): a row's frame is the normal at its nearest surface point\n",
+                this->normals_ ? this->normals_->size() : (size_t)0, surf.size());
+      return;
+    }
+    const detail::SoA s = detail::soa_xyz(surf), nrm = detail::soa_normals(*this->normals_);
+    const detail::SoA q = detail::soa_xyz(*this->input_);
+    const size_t nq = this->input_->size();
+    std::vector<float> d(nq * 1980), rf(nq * 9), rnd(nq * 3);
+    // drawn ahead: three floats for every row; the rows that draw take them in order
+    pfx_rng_uniform01(seed_, stream_pos_, (int64_t)rnd.size(), rnd.data());
+    if (!detail::ok(pfx_shape_context(detail::context(), s.x.data(), s.y.data(), s.z.data(), nrm.x.data(),
+                                      nrm.y.data(), nrm.z.data(), (int64_t)surf.size(), q.x.data(), q.y.data(),
+                                      q.z.data(), (int64_t)nq, this->search_radius_, min_radius_,
+                                      point_density_radius_, rnd.data(), d.data(), rf.data()),
+                    "ShapeContext3DEstimation"))
+      return;
+    int64_t draws = 0;
+    if (!detail::ok(pfx_ctx_last_stats(detail::context(), "sc_draws", &draws), "ShapeContext3DEstimation")) return;
+    stream_pos_ += 3 * draws;
+    detail::sc_rows(d, rf, nq, out);
+  }
+  double min_radius_ = 0.1, point_density_radius_ = 0.2;
+  uint32_t seed_;
+  int64_t stream_pos_ = 0;  // floats of the stream already used
+};
+
+// SHOTLocalReferenceFrameEstimation<In, ReferenceFrame>: SHOT's frames alone (a NaN frame where
+// fewer than five neighbours define it)
+template <typename PointInT, typename PointOutT = ReferenceFrame>
+class SHOTLocalReferenceFrameEstimation : public Feature<PointInT, PointOutT> {
+ public:
+  typedef std::shared_ptr<SHOTLocalReferenceFrameEstimation<PointInT, PointOutT> > Ptr;
+  typedef std::shared_ptr<const SHOTLocalReferenceFrameEstimation<PointInT, PointOutT> > ConstPtr;
+  SHOTLocalReferenceFrameEstimation() { this->name_ = "SHOTLocalReferenceFrameEstimation"; }
+
+ protected:
+  void computeFeature(PointCloud<PointOutT>& out) override {
+    static_assert(sizeof(PointOutT) == sizeof(float) * 9, "a ReferenceFrame output");
+    const detail::SoA s = detail::soa_xyz(this->surface()), q = detail::soa_xyz(*this->input_);
+    const size_t nq = this->input_->size();
+    std::vector<float> rf(nq * 9);
+    if (!detail::ok(pfx_shot_lrf(detail::context(), s.x.data(), s.y.data(), s.z.data(), (int64_t)s.x.size(),
+                                 q.x.data(), q.y.data(), q.z.data(), (int64_t)nq, this->search_radius_, rf.data()),
+                    "SHOTLocalReferenceFrameEstimation"))
+      return;
+    out.resize(nq);
+    out.is_dense = true;
+    for (size_t i = 0; i < nq; ++i) {
+      for (int b = 0; b < 3; ++b) {
+        out.points[i].x_axis[b] = rf[i * 9 + b];
+        out.points[i].y_axis[b] = rf[i * 9 + 3 + b];
+        out.points[i].z_axis[b] = rf[i * 9 + 6 + b];
+      }
+      if (std::isnan(rf[i * 9])) out.is_dense = false;
+    }
+  }
+};
+
+// UniqueShapeContext<In, ShapeContext1980, ReferenceFrame>.  Without input frames it computes them
+// with SHOTLocalReferenceFrameEstimation at the local radius (PCL's default: 2.5) over the search
+// surface.  That frame search has SHOT's capacity, 16,384 neighbours: on a cloud where the local
+// radius reaches more, compute() fails with that message (set a smaller local radius or frames).
+template <typename PointInT, typename PointOutT = ShapeContext1980, typename PointRFT = ReferenceFrame>
+class UniqueShapeContext : public Feature<PointInT, PointOutT> {
+ public:
+  typedef PointCloud<PointRFT> PointCloudLRF;
+  typedef typename PointCloudLRF::ConstPtr PointCloudLRFConstPtr;
+  typedef std::shared_ptr<UniqueShapeContext<PointInT, PointOutT, PointRFT> > Ptr;
+  UniqueShapeContext() { this->name_ = "UniqueShapeContext"; }
+  void setMinimalRadius(double radius) { min_radius_ = radius; }
+  double getMinimalRadius() const { return min_radius_; }
+  void setPointDensityRadius(double radius) { point_density_radius_ = radius; }
+  double getPointDensityRadius() const { return point_density_radius_; }
+  void setLocalRadius(double radius) { local_radius_ = radius; }
+  double getLocalRadius() const { return local_radius_; }
+  void setInputReferenceFrames(const PointCloudLRFConstPtr& frames) { frames_ = frames; }
+  PointCloudLRFConstPtr getInputReferenceFrames() const { return frames_; }
+
+ protected:
+  void computeFeature(PointCloud<PointOutT>& out) override {
+    const size_t nq = this->input_->size();
+    if (!detail::sc_radii_ok("UniqueShapeContext", this->search_radius_, min_radius_, point_density_radius_)) return;
+    if (frames_ && frames_->size() != nq) {
+      PCL_ERROR("[pcl::UniqueShapeContext::compute] the number of input reference frames (%zu) differs from the "
+                "input cloud's points (%zu)\n", frames_->size(), nq);
+      return;
+    }
+    const detail::SoA s = detail::soa_xyz(this->surface()), q = detail::soa_xyz(*this->input_);
+    std::vector<float> fr(nq * 9), d(nq * 1980), rf(nq * 9);
+    if (frames_) {
+      for (size_t i = 0; i < nq; ++i)
+        for (int b = 0; b < 3; ++b) {
+          fr[i * 9 + b] = frames_->points[i].x_axis[b];
+          fr[i * 9 + 3 + b] = frames_->points[i].y_axis[b];
+          fr[i * 9 + 6 + b] = frames_->points[i].z_axis[b];
+        }
+    } else {
+      if (!(local_radius_ > 0.0)) {
+        PCL_ERROR("[pcl::UniqueShapeContext::compute] the local radius must be positive\n");
+        return;
+      }
+      const pfx_status st = pfx_shot_lrf(detail::context(), s.x.data(), s.y.data(), s.z.data(), (int64_t)s.x.size(),
+                                         q.x.data(), q.y.data(), q.z.data(), (int64_t)nq, local_radius_, fr.data());
+      if (st == PFX_ERR_CAPACITY) {
+        PCL_ERROR("[pcl::UniqueShapeContext::compute] the reference frames at the local radius %g exceed the frame "
+                  "search's capacity of 16384 neighbours (%s): set a smaller local radius with setLocalRadius or "
+                  "give frames with setInputReferenceFrames\n", local_radius_, pfx_last_error(detail::context()));
+        return;
+      }
+      if (!detail::ok(st, "UniqueShapeContext")) return;
+    }
+    if (!detail::ok(pfx_usc(detail::context(), s.x.data(), s.y.data(), s.z.data(), (int64_t)s.x.size(), q.x.data(),
+                            q.y.data(), q.z.data(), fr.data(), (int64_t)nq, this->search_radius_, min_radius_,
+                            point_density_radius_, d.data(), rf.data()),
+                    "UniqueShapeContext"))
+      return;
+    detail::sc_rows(d, rf, nq, out);
+  }
+  double min_radius_ = 0.1, point_density_radius_ = 0.2, local_radius_ = 2.5;
+  PointCloudLRFConstPtr frames_;
+};
+
 // ---- range image + NARF (keypoints.h:203-224) ---------------------------------------------
 class RangeImage : public PointCloud<PointWithRange> {
  public:
@@ -1076,6 +1251,7 @@ template <typename T> struct DescriptorLayout;
 template <> struct DescriptorLayout<FPFHSignature33> { static constexpr int dim = 33, stride = 33; };
 template <> struct DescriptorLayout<SHOT352> { static constexpr int dim = 352, stride = 361; };
 template <> struct DescriptorLayout<SHOT1344> { static constexpr int dim = 1344, stride = 1353; };
+template <> struct DescriptorLayout<ShapeContext1980> { static constexpr int dim = 1980, stride = 1989; };
 template <> struct DescriptorLayout<PFHSignature125> { static constexpr int dim = 125, stride = 125; };
 template <int N> struct DescriptorLayout<Histogram<N> > { static constexpr int dim = N, stride = N; };
 // (DefaultPointRepresentation<IntensityGradient>: the three gradient floats of a 16-byte point)

@@ -153,6 +153,17 @@ _SIGS = {
                          ctypes.c_int32, ctypes.c_int32, c_vp]),
     "pfx_rift_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
                              ctypes.c_int32, ctypes.c_int32, c_vp]),
+    "pfx_shape_context": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
+                                  c_dbl, c_dbl, c_vp, c_vp, c_vp]),
+    "pfx_shape_context_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
+                                      c_dbl, c_dbl, c_vp, c_vp, c_vp]),
+    "pfx_usc": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_vp,
+                        c_vp]),
+    "pfx_usc_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_vp,
+                            c_vp]),
+    "pfx_shot_lrf": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl, c_vp]),
+    "pfx_shot_lrf_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl, c_vp]),
+    "pfx_rng_uniform01": (c_int, [ctypes.c_uint32, c_i64, c_i64, c_vp]),
     "pfx_range_image_planar": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(Camera), c_vp]),
     "pfx_narf_keypoints": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(Camera),
                                    ctypes.POINTER(NarfParams), c_vp, c_i64, c_i64p]),
@@ -206,11 +217,13 @@ _SIGS = {
 }
 
 # entry points an older library loaded through PFX_LIB (A/B runs against a previous build) may lack:
-# test hooks, ICP, spin images, intensity gradients and RIFT (calling a missing one raises
-# AttributeError there)
+# test hooks, ICP, spin images, intensity gradients, RIFT and the shape contexts (calling a missing one
+# raises AttributeError there)
 _OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_icp_dev",
                    "pfx_spin_params_default", "pfx_spin_image", "pfx_spin_image_dev",
-                   "pfx_intensity_gradient", "pfx_intensity_gradient_dev", "pfx_rift", "pfx_rift_dev"}
+                   "pfx_intensity_gradient", "pfx_intensity_gradient_dev", "pfx_rift", "pfx_rift_dev",
+                   "pfx_shape_context", "pfx_shape_context_dev", "pfx_usc", "pfx_usc_dev", "pfx_shot_lrf",
+                   "pfx_shot_lrf_dev", "pfx_rng_uniform01"}
 
 _lib = None
 

@@ -56,6 +56,16 @@ def icp_params(**kw) -> N.IcpParams:
     return p
 
 
+def uniform01_stream(seed, n, skip=0) -> np.ndarray:
+    """n float32 of the shape context's random stream (boost::mt19937 seeded `seed`, read through
+    uniform_01<float>) after skipping `skip` floats (pfx_rng_uniform01; host only)."""
+    out = np.empty(int(n), dtype=np.float32)
+    code = N.lib().pfx_rng_uniform01(int(seed) & 0xffffffff, int(skip), int(n), _ptr(out))
+    if code != 0:
+        raise N.PfxError(code, "uniform01_stream: skip and n must be >= 0")
+    return out
+
+
 def spin_params(image_width=8, support_angle_cos=0.0, min_pts_neighb=0, radial=0, angular=0) -> N.SpinParams:
     """pfx_spin_params; the defaults are PCL's (pfx_spin_params_default)."""
     p = N.SpinParams()
@@ -301,6 +311,52 @@ class Context:
                                        _ptr(cx), _ptr(cy), _ptr(cz), nq, float(r), D, G, _ptr(out)))
         return out
 
+    def shape_context(self, sx, sy, sz, nx, ny, nz, qx, qy, qz, r, min_radius=None, point_density_radius=None,
+                      rnd=None):
+        """ShapeContext3DEstimation (pfx_shape_context): desc (nq, 1980) and rf (nq, 9) float32.  The
+        minimal and point-density radii default to r / 10 and r / 5.  rnd: (3 nq) float32, three per
+        drawing row (uniform01_stream); None starts the stream of seed 12345 afresh."""
+        sx, sy, sz, nx, ny, nz, qx, qy, qz = map(_f32, (sx, sy, sz, nx, ny, nz, qx, qy, qz))
+        nq = len(qx)
+        if len(nx) != len(sx):
+            raise ValueError("shape_context: one normal per surface point")
+        if rnd is not None:
+            rnd = _f32(rnd).ravel()
+            if len(rnd) != 3 * nq:
+                raise ValueError("shape_context: rnd holds three floats per query")
+        rmin = float(r) / 10 if min_radius is None else float(min_radius)
+        rho = float(r) / 5 if point_density_radius is None else float(point_density_radius)
+        desc = np.empty((nq, 1980), dtype=np.float32)
+        rf = np.empty((nq, 9), dtype=np.float32)
+        self._check(self._lib.pfx_shape_context(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(nx), _ptr(ny), _ptr(nz),
+                                                len(sx), _ptr(qx), _ptr(qy), _ptr(qz), nq, float(r), rmin, rho,
+                                                _ptr(rnd), _ptr(desc), _ptr(rf)))
+        return desc, rf
+
+    def usc(self, sx, sy, sz, qx, qy, qz, frames, r, min_radius=None, point_density_radius=None):
+        """UniqueShapeContext (pfx_usc) with the caller's frames, (nq, 9) float32 (x, y, z axis: shot_lrf's
+        layout): desc (nq, 1980) and rf (nq, 9) float32."""
+        sx, sy, sz, qx, qy, qz = map(_f32, (sx, sy, sz, qx, qy, qz))
+        nq = len(qx)
+        frames = _f32(frames).ravel()
+        if len(frames) != 9 * nq:
+            raise ValueError("usc: one frame of nine floats per query")
+        rmin = float(r) / 10 if min_radius is None else float(min_radius)
+        rho = float(r) / 5 if point_density_radius is None else float(point_density_radius)
+        desc = np.empty((nq, 1980), dtype=np.float32)
+        rf = np.empty((nq, 9), dtype=np.float32)
+        self._check(self._lib.pfx_usc(self.h, _ptr(sx), _ptr(sy), _ptr(sz), len(sx), _ptr(qx), _ptr(qy), _ptr(qz),
+                                      _ptr(frames), nq, float(r), rmin, rho, _ptr(desc), _ptr(rf)))
+        return desc, rf
+
+    def shot_lrf(self, sx, sy, sz, qx, qy, qz, r):
+        """SHOTLocalReferenceFrameEstimation (pfx_shot_lrf): (nq, 9) float32, shot()'s rf bit for bit."""
+        sx, sy, sz, qx, qy, qz = map(_f32, (sx, sy, sz, qx, qy, qz))
+        rf = np.empty((len(qx), 9), dtype=np.float32)
+        self._check(self._lib.pfx_shot_lrf(self.h, _ptr(sx), _ptr(sy), _ptr(sz), len(sx), _ptr(qx), _ptr(qy),
+                                           _ptr(qz), len(qx), float(r), _ptr(rf)))
+        return rf
+
     def range_image_planar(self, x, y, z, cam=None):
         cam = cam or camera()
         x, y, z = map(_f32, (x, y, z))
@@ -488,6 +544,32 @@ class Context:
         self._check(self._lib.pfx_rift_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(sgx), _ptr(sgy), _ptr(sgz),
                                            sx.numel(), _ptr(cx), _ptr(cy), _ptr(cz), cx.numel(), float(r),
                                            int(nr_distance_bins), int(nr_gradient_bins), _ptr(out)))
+
+    def shape_context_dev(self, sx, sy, sz, nx, ny, nz, qx, qy, qz, r, desc, rf, min_radius=None,
+                          point_density_radius=None, rnd=None):
+        """pfx_shape_context_dev: desc (nq, 1980) and rf (nq, 9) float32 device tensors, rnd an optional
+        (3 nq) float32 device tensor; a neighbourhood beyond capacity is reported by the next
+        synchronize()."""
+        rmin = float(r) / 10 if min_radius is None else float(min_radius)
+        rho = float(r) / 5 if point_density_radius is None else float(point_density_radius)
+        self._check(self._lib.pfx_shape_context_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(nx), _ptr(ny),
+                                                    _ptr(nz), sx.numel(), _ptr(qx), _ptr(qy), _ptr(qz), qx.numel(),
+                                                    float(r), rmin, rho, _ptr(rnd), _ptr(desc), _ptr(rf)))
+
+    def usc_dev(self, sx, sy, sz, qx, qy, qz, frames, r, desc, rf, min_radius=None, point_density_radius=None):
+        """pfx_usc_dev: frames (nq, 9), desc (nq, 1980) and rf (nq, 9) float32 device tensors; a
+        neighbourhood beyond capacity is reported by the next synchronize()."""
+        rmin = float(r) / 10 if min_radius is None else float(min_radius)
+        rho = float(r) / 5 if point_density_radius is None else float(point_density_radius)
+        self._check(self._lib.pfx_usc_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), sx.numel(), _ptr(qx), _ptr(qy),
+                                          _ptr(qz), _ptr(frames), qx.numel(), float(r), rmin, rho, _ptr(desc),
+                                          _ptr(rf)))
+
+    def shot_lrf_dev(self, sx, sy, sz, qx, qy, qz, r, rf):
+        """pfx_shot_lrf_dev: rf is an (nq, 9) float32 device tensor; a neighbourhood beyond capacity is
+        reported by the next synchronize()."""
+        self._check(self._lib.pfx_shot_lrf_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), sx.numel(), _ptr(qx), _ptr(qy),
+                                               _ptr(qz), qx.numel(), float(r), _ptr(rf)))
 
     def narf_keypoints_dev(self, x, y, z, params=None, cam=None, cap=1 << 20):
         cam = cam or camera()

@@ -110,6 +110,7 @@ pfx_status pfx_ctx_create(int device, pfx_ctx** out) {
     ctx->stats["spin_cap_small"] = pfx::spin_cap_small();
     ctx->stats["spin_chunk"] = pfx::spin_chunk();
     ctx->stats["rift_cap_small"] = pfx::rift_cap_small();
+    ctx->stats["sc_cap_small"] = pfx::sc_cap_small();
     // grid builds by builder (pfx_grid.hip), and speculative counting builds that met a fat cell
     for (const char* s : {"grid_count_builds", "grid_sort_builds", "grid_hinted_sort_builds", "grid_fat_fallbacks"})
       ctx->stats[s] = 0;
@@ -145,6 +146,7 @@ void pfx_ctx_destroy(pfx_ctx* ctx) {
   if (ctx->pfh_rb_mem) (void)hipHostFree(ctx->pfh_rb_mem);
   if (ctx->spin_rb_mem) (void)hipHostFree(ctx->spin_rb_mem);
   if (ctx->rift_rb_mem) (void)hipHostFree(ctx->rift_rb_mem);
+  if (ctx->sc_rb_mem) (void)hipHostFree(ctx->sc_rb_mem);
   delete ctx;
 }
 
@@ -192,6 +194,7 @@ pfx_status pfx_ctx_trim(pfx_ctx* ctx) {
   pfx::pfh_resolve(ctx);
   pfx::spin_resolve(ctx);
   pfx::rift_resolve(ctx);
+  pfx::sc_resolve(ctx);
   pfx::narf_release(ctx);
   pfx::normals_release(ctx);
   pfx::keypoints_release(ctx);
@@ -215,6 +218,7 @@ pfx_status pfx_ctx_synchronize(pfx_ctx* ctx) {
   pfx::pfh_resolve(ctx);
   pfx::spin_resolve(ctx);
   pfx::rift_resolve(ctx);
+  pfx::sc_resolve(ctx);
   PFX_API_END(ctx)
 }
 
@@ -256,12 +260,14 @@ pfx_status pfx_ctx_kernel_time(pfx_ctx* ctx, const char* name, double* total_ms,
 pfx_status pfx_ctx_last_stats(pfx_ctx* ctx, const char* what, int64_t* value) {
   PFX_API_BEGIN
   if (!ctx || !what || !value) throw Error(PFX_ERR_INVALID, "null argument");
-  if (ctx->fpfh_pending || ctx->pfh_pending || ctx->spin_pending || ctx->igrad_pending || ctx->rift_pending) {
+  if (ctx->fpfh_pending || ctx->pfh_pending || ctx->spin_pending || ctx->igrad_pending || ctx->rift_pending ||
+      ctx->sc_pending || ctx->lrf_pending) {
     PFX_HIP(hipStreamSynchronize(ctx->stream));
     pfx::fpfh_resolve(ctx);
     pfx::pfh_resolve(ctx);
     pfx::spin_resolve(ctx);
     pfx::rift_resolve(ctx);
+    pfx::sc_resolve(ctx);
   }
   auto it = ctx->stats.find(what);
   if (it == ctx->stats.end()) throw Error(PFX_ERR_INVALID, std::string("unknown stat ") + what);
@@ -854,6 +860,147 @@ pfx_status pfx_rift(pfx_ctx* ctx, const float* sx, const float* sy, const float*
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   pfx::rift_resolve(ctx);  // the host API reports at once
   PFX_API_END(ctx)
+}
+
+// every check that precedes a launch (host and device entry points alike)
+static void sc_check(const char* what, const float* sx, const float* sy, const float* sz, bool normals_ok,
+                     int64_t n_surface, const float* qx, const float* qy, const float* qz, bool frames_ok,
+                     int64_t nq, double radius, double min_radius, double density_radius, const float* desc,
+                     const float* rf) {
+  if (n_surface < 0 || nq < 0 || (nq && (!desc || !rf || !qx || !qy || !qz || !frames_ok)) ||
+      (n_surface && (!sx || !sy || !sz || !normals_ok)))
+    throw Error(PFX_ERR_INVALID, std::string(what) + ": invalid arguments");
+  if (!(radius > 0.0) || !(min_radius > 0.0) || !(density_radius > 0.0))
+    throw Error(PFX_ERR_INVALID, std::string(what) + ": every radius must be > 0");
+  if (radius < min_radius)  // PCL's initCompute refuses this
+    throw Error(PFX_ERR_INVALID, std::string(what) + ": the search radius is below the minimal radius");
+}
+
+pfx_status pfx_shape_context_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                                 const float* d_snx, const float* d_sny, const float* d_snz, int64_t n_surface,
+                                 const float* d_qx, const float* d_qy, const float* d_qz, int64_t nq,
+                                 double radius, double min_radius, double point_density_radius,
+                                 const float* d_rnd, float* d_desc, float* d_rf) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  sc_check("shape_context", d_sx, d_sy, d_sz, d_snx && d_sny && d_snz, n_surface, d_qx, d_qy, d_qz, true, nq,
+           radius, min_radius, point_density_radius, d_desc, d_rf);
+  pfx::sc_dev(ctx, d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, nullptr, nq, radius,
+              min_radius, point_density_radius, d_rnd, d_desc, d_rf);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_shape_context(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
+                             const float* sny, const float* snz, int64_t n_surface, const float* qx,
+                             const float* qy, const float* qz, int64_t nq, double radius, double min_radius,
+                             double point_density_radius, const float* rnd, float* desc, float* rf) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  sc_check("shape_context", sx, sy, sz, snx && sny && snz, n_surface, qx, qy, qz, true, nq, radius, min_radius,
+           point_density_radius, desc, rf);
+  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
+  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
+  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
+  float* dnx = stage_in(ctx, "in_nx", snx, n_surface);
+  float* dny = stage_in(ctx, "in_ny", sny, n_surface);
+  float* dnz = stage_in(ctx, "in_nz", snz, n_surface);
+  float* dqx = stage_in(ctx, "in_qx", qx, nq);
+  float* dqy = stage_in(ctx, "in_qy", qy, nq);
+  float* dqz = stage_in(ctx, "in_qz", qz, nq);
+  float* drnd = rnd ? stage_in(ctx, "in_sc_rnd", rnd, 3 * nq) : nullptr;
+  float* ddesc = ctx->buf("out_sc").as<float>(nq * 1980 + 1);
+  float* drf = ctx->buf("out_sc_rf").as<float>(nq * 9 + 1);
+  pfx::sc_dev(ctx, dsx, dsy, dsz, dnx, dny, dnz, n_surface, dqx, dqy, dqz, nullptr, nq, radius, min_radius,
+              point_density_radius, drnd, ddesc, drf);
+  if (nq) {
+    PFX_HIP(hipMemcpyAsync(desc, ddesc, sizeof(float) * nq * 1980, hipMemcpyDeviceToHost, ctx->stream));
+    PFX_HIP(hipMemcpyAsync(rf, drf, sizeof(float) * nq * 9, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  pfx::sc_resolve(ctx);  // the host API reports at once
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_usc_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz, int64_t n_surface,
+                       const float* d_qx, const float* d_qy, const float* d_qz, const float* d_frames, int64_t nq,
+                       double radius, double min_radius, double point_density_radius, float* d_desc,
+                       float* d_rf) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  sc_check("usc", d_sx, d_sy, d_sz, true, n_surface, d_qx, d_qy, d_qz, d_frames != nullptr, nq, radius, min_radius,
+           point_density_radius, d_desc, d_rf);
+  pfx::sc_dev(ctx, d_sx, d_sy, d_sz, nullptr, nullptr, nullptr, n_surface, d_qx, d_qy, d_qz, d_frames, nq, radius,
+              min_radius, point_density_radius, nullptr, d_desc, d_rf);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_usc(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t n_surface,
+                   const float* qx, const float* qy, const float* qz, const float* frames, int64_t nq,
+                   double radius, double min_radius, double point_density_radius, float* desc, float* rf) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  sc_check("usc", sx, sy, sz, true, n_surface, qx, qy, qz, frames != nullptr, nq, radius, min_radius,
+           point_density_radius, desc, rf);
+  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
+  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
+  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
+  float* dqx = stage_in(ctx, "in_qx", qx, nq);
+  float* dqy = stage_in(ctx, "in_qy", qy, nq);
+  float* dqz = stage_in(ctx, "in_qz", qz, nq);
+  float* dfr = stage_in(ctx, "in_sc_frames", frames, 9 * nq);
+  float* ddesc = ctx->buf("out_sc").as<float>(nq * 1980 + 1);
+  float* drf = ctx->buf("out_sc_rf").as<float>(nq * 9 + 1);
+  if (nq) {
+    pfx::sc_dev(ctx, dsx, dsy, dsz, nullptr, nullptr, nullptr, n_surface, dqx, dqy, dqz, dfr, nq, radius, min_radius,
+                point_density_radius, nullptr, ddesc, drf);
+    PFX_HIP(hipMemcpyAsync(desc, ddesc, sizeof(float) * nq * 1980, hipMemcpyDeviceToHost, ctx->stream));
+    PFX_HIP(hipMemcpyAsync(rf, drf, sizeof(float) * nq * 9, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  pfx::sc_resolve(ctx);  // the host API reports at once
+  PFX_API_END(ctx)
+}
+
+static void lrf_check(const float* sx, const float* sy, const float* sz, int64_t n_surface, const float* qx,
+                      const float* qy, const float* qz, int64_t nq, double radius, const float* rf) {
+  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!rf || !qx || !qy || !qz)) ||
+      (n_surface && (!sx || !sy || !sz)))
+    throw Error(PFX_ERR_INVALID, "shot_lrf: invalid arguments");
+}
+
+pfx_status pfx_shot_lrf_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                            int64_t n_surface, const float* d_qx, const float* d_qy, const float* d_qz, int64_t nq,
+                            double radius, float* d_rf) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  lrf_check(d_sx, d_sy, d_sz, n_surface, d_qx, d_qy, d_qz, nq, radius, d_rf);
+  pfx::shot_lrf_dev(ctx, d_sx, d_sy, d_sz, n_surface, d_qx, d_qy, d_qz, nq, radius, d_rf);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_shot_lrf(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t n_surface,
+                        const float* qx, const float* qy, const float* qz, int64_t nq, double radius, float* rf) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  lrf_check(sx, sy, sz, n_surface, qx, qy, qz, nq, radius, rf);
+  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
+  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
+  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
+  float* dqx = stage_in(ctx, "in_qx", qx, nq);
+  float* dqy = stage_in(ctx, "in_qy", qy, nq);
+  float* dqz = stage_in(ctx, "in_qz", qz, nq);
+  float* drf = ctx->buf("out_sc_rf").as<float>(nq * 9 + 1);
+  pfx::shot_lrf_dev(ctx, dsx, dsy, dsz, n_surface, dqx, dqy, dqz, nq, radius, drf);
+  if (nq) PFX_HIP(hipMemcpyAsync(rf, drf, sizeof(float) * nq * 9, hipMemcpyDeviceToHost, ctx->stream));
+  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  pfx::sc_resolve(ctx);  // the host API reports at once
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_rng_uniform01(uint32_t seed, int64_t skip, int64_t n, float* out) {
+  if (skip < 0 || n < 0 || (n && !out)) return PFX_ERR_INVALID;
+  pfx::rng_uniform01(seed, skip, n, out);
+  return PFX_OK;
 }
 
 pfx_status pfx_range_image_planar(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,

@@ -189,6 +189,10 @@ struct pfx_ctx {
   // igrad_dev's and rift_dev's, the same way (pfx::rift_resolve)
   void* rift_rb_mem = nullptr;
   bool igrad_pending = false, rift_pending = false;
+  // sc_dev's and shot_lrf_dev's, the same way (pfx::sc_resolve)
+  void* sc_rb_mem = nullptr;
+  bool sc_pending = false, lrf_pending = false;
+  int64_t sc_rnd_n = 0;  // floats of the default random stream held in buf("sc_rnd")
   // one side stream + fork/join events (normal estimation's long-list chains), created on first use
   hipStream_t side = nullptr;
   hipEvent_t fork_ev[2] = {nullptr, nullptr};
@@ -388,6 +392,18 @@ void rift_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, c
               int64_t nq, double r, int D, int G, float* out);
 void rift_resolve(pfx_ctx* ctx);
 int rift_cap_small();  // neighbours of the first pass (stat "rift_cap_small")
+// 3D shape contexts, unique shape contexts and SHOT's frames alone (pfx_shape_context.hip): errors
+// and statistics as spin images (sc_resolve serves the three).  sc_dev: frames == nullptr is the
+// 3DSC (normals read; rnd nullable: the stream of seed 12345 from its start), else USC.
+void sc_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx, const float* sny,
+            const float* snz, int64_t ns, const float* qx, const float* qy, const float* qz, const float* frames,
+            int64_t nq, double R, double rmin, double rho, const float* rnd, float* desc, float* rf);
+void shot_lrf_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, const float* qx,
+                  const float* qy, const float* qz, int64_t nq, double r, float* rf);
+void sc_resolve(pfx_ctx* ctx);
+int sc_cap_small();  // neighbours of the first pass (stat "sc_cap_small")
+// boost::mt19937 through uniform_01<float>: n floats of the stream of `seed` after `skip` floats
+void rng_uniform01(uint32_t seed, int64_t skip, int64_t n, float* out);
 void range_image_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
                      const pfx_camera& cam, float4* d_points);
 int64_t narf_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
