@@ -36,6 +36,10 @@
  *                          (features.h:175-196, evaluation.cpp:319-345)
  *   pfx_usc*            <- UniqueShapeContext<PointXYZRGB,ShapeContext1980>::compute
  *                          (evaluation.cpp:346-371); pfx_shot_lrf* its frames
+ *   pfx_moment_invariants* <- MomentInvariantsEstimation<PointXYZRGB,MomentInvariants>::compute
+ *                          (features.h:175-196, evaluation.cpp:554-572)
+ *   pfx_principal_curvatures* <- PrincipalCurvaturesEstimation<PointXYZRGB,Normal,
+ *                          PrincipalCurvatures>::compute (features.h:175-196, evaluation.cpp:696-715)
  *   pfx_range_image_planar* <- RangeImagePlanar::createFromPointCloudWithFixedSize
  *                          (keypoints.h:212-216, tools.h:61-77)
  *   pfx_narf_keypoints* <- RangeImageBorderExtractor + NarfKeypoint::compute
@@ -550,6 +554,54 @@ pfx_status pfx_shot_lrf_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, 
  * uniform_01<float> (v = (float)u32 / 2^32, drawn again unless v < 1), after skipping `skip`
  * floats. */
 pfx_status pfx_rng_uniform01(uint32_t seed, int64_t skip, int64_t n, float* out);
+
+/* ---- moment invariants: MomentInvariantsEstimation<PointXYZRGB, MomentInvariants>
+ *      (evaluation.cpp:554-572) and principal curvatures: PrincipalCurvaturesEstimation<PointXYZRGB,
+ *      Normal, PrincipalCurvatures> (evaluation.cpp:696-715) --------------------------------- */
+/* Both read the radius neighbours of query i in the surface, in FLANN order, all in float32 with
+ * no FMA contraction.  DESIGN.md "Moments and curvatures: the contract" states every operation;
+ * the CPU restatement of that text is the truth the kernels are tested against (parity with PCL
+ * itself is unpinned).
+ * pfx_moment_invariants: out is nq x 3 floats, j1 j2 j3.  The centroid (three sequential sums,
+ * each times 1 / float(k)); with t the neighbour minus the centroid, the six sequential sums mu200
+ * mu020 mu002 mu110 mu101 mu011 of t0 t0, t1 t1, t2 t2, t0 t1, t0 t2, t1 t2; then
+ *   j1 = mu200 + mu020 + mu002
+ *   j2 = mu200 mu020 + mu200 mu002 + mu020 mu002 - mu110^2 - mu101^2 - mu011^2
+ *   j3 = mu200 mu020 mu002 + 2 mu110 mu101 mu011 - mu002 mu110^2 - mu020 mu101^2 - mu200 mu011^2
+ * left to right.  k = 1 gives 0 0 0.
+ * pfx_principal_curvatures: out is nq x 5 floats, the principal direction x y z, then pc1 and pc2.
+ * (snx, sny, snz) are the surface normals and n = (qnx, qny, qnz)[i] the caller's query normal, as
+ * for the spin-image axis.  Every neighbour normal is projected by M = Identity - n n^T; the
+ * centroid of the projections (sequential sums, times 1 / float(k)) and the six upper sums of
+ * their covariance follow; pcl::eigen33 gives its eigenvalues (ascending),
+ * pcl::computeCorrespondingEigenVector the direction of the largest; pc1 and pc2 are the largest
+ * and the middle eigenvalue times 1 / float(k).  Equal normals in the ball (k = 1 included) give
+ * pc1 = pc2 = 0 and a NaN direction (0 / 0), PCL's result.  A NaN query normal or a NaN normal
+ * among the neighbours gives whatever that arithmetic gives.
+ * Both: k = 0 (a non-finite query included) is a NaN row; every NaN is written as 0x7fc00000.
+ * Null pointers, negative sizes or radius <= 0: PFX_ERR_INVALID before any launch; nq == 0
+ * succeeds without a launch.  One workgroup serves a query, with at most 16384 neighbours
+ * (PFX_ERR_CAPACITY beyond, reported as the spin image's late errors are).  Statistics:
+ * "moments_neighbors" / "pcurv_neighbors" (sum of k), "moments_kmax" / "pcurv_kmax",
+ * "moments_queued" / "pcurv_queued" (rows with more than "moments_cap_small" neighbours, which take
+ * the second pass); "moments_cap_small" can be read from a new ctx. */
+pfx_status pfx_moment_invariants(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz,
+                                 int64_t n_surface, const float* qx, const float* qy, const float* qz,
+                                 int64_t nq, double radius, float* out);
+pfx_status pfx_principal_curvatures(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz,
+                                    const float* snx, const float* sny, const float* snz, int64_t n_surface,
+                                    const float* qx, const float* qy, const float* qz, const float* qnx,
+                                    const float* qny, const float* qnz, int64_t nq, double radius, float* out);
+/* Device pointers, stream-ordered on the ctx stream, no host synchronisation; late errors and
+ * statistics as pfx_spin_image_dev. */
+pfx_status pfx_moment_invariants_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                                     int64_t n_surface, const float* d_qx, const float* d_qy, const float* d_qz,
+                                     int64_t nq, double radius, float* d_out);
+pfx_status pfx_principal_curvatures_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                                        const float* d_snx, const float* d_sny, const float* d_snz,
+                                        int64_t n_surface, const float* d_qx, const float* d_qy,
+                                        const float* d_qz, const float* d_qnx, const float* d_qny,
+                                        const float* d_qnz, int64_t nq, double radius, float* d_out);
 
 /* ---- range image + NARF keypoints ---------------------------------------------------- */
 /* out_points: width*height x 4 floats {x, y, z, range} (PointWithRange); unobserved pixels

@@ -199,6 +199,20 @@ struct alignas(16) IntensityGradient {
   IntensityGradient() : gradient{0, 0, 0} {}
 };
 static_assert(sizeof(IntensityGradient) == 16, "pcl::IntensityGradient is 16 bytes");
+// pcl::MomentInvariants: j1 j2 j3, 12 bytes
+struct MomentInvariants { float j1 = 0, j2 = 0, j3 = 0; };
+static_assert(sizeof(MomentInvariants) == 12, "pcl::MomentInvariants is 12 bytes");
+// pcl::PrincipalCurvatures: 20 bytes, the direction of the largest curvature as an array and by
+// name, then the largest and the smallest curvature
+struct PrincipalCurvatures {
+  union {
+    float principal_curvature[3];
+    struct { float principal_curvature_x, principal_curvature_y, principal_curvature_z; };
+  };
+  float pc1 = 0, pc2 = 0;
+  PrincipalCurvatures() : principal_curvature{0, 0, 0} {}
+};
+static_assert(sizeof(PrincipalCurvatures) == 20, "pcl::PrincipalCurvatures is 20 bytes");
 struct FPFHSignature33 { float histogram[33]; };
 struct PFHSignature125 { float histogram[125]; };
 // pcl::Histogram<N> (spin images, RIFT, and later intensity spin): N floats, nothing else
@@ -668,6 +682,87 @@ class IntensityGradientEstimation : public FeatureFromNormals<PointInT, PointNT,
     for (size_t i = 0; i < nq; ++i) {
       for (int c = 0; c < 3; ++c) out.points[i].gradient[c] = g[3 * i + (size_t)c];
       if (std::isnan(g[3 * i])) out.is_dense = false;
+    }
+  }
+};
+
+// MomentInvariantsEstimation<PointXYZRGB, MomentInvariants> (evaluation.cpp:554-572): a plain Feature,
+// so Features<T>::compute's cast (features.h:175-196) computes no normals for it.  Row i is j1 j2 j3
+// of the radius neighbours of input point i in the surface; a row without neighbours is NaN.
+template <typename PointInT, typename PointOutT>
+class MomentInvariantsEstimation : public Feature<PointInT, PointOutT> {
+ public:
+  typedef std::shared_ptr<MomentInvariantsEstimation<PointInT, PointOutT> > Ptr;
+  MomentInvariantsEstimation() { this->name_ = "MomentInvariantsEstimation"; }
+
+ protected:
+  void computeFeature(PointCloud<PointOutT>& out) override {
+    const PointCloud<PointInT>& surf = this->surface();
+    const size_t nq = this->input_->size(), ns = surf.size();
+    const detail::SoA s = detail::soa_xyz(surf), q = detail::soa_xyz(*this->input_);
+    std::vector<float> j(nq * 3);
+    if (!detail::ok(pfx_moment_invariants(detail::context(), s.x.data(), s.y.data(), s.z.data(), (int64_t)ns,
+                                          q.x.data(), q.y.data(), q.z.data(), (int64_t)nq, this->search_radius_,
+                                          j.data()),
+                    "MomentInvariantsEstimation"))
+      return;
+    out.resize(nq);
+    out.is_dense = true;
+    for (size_t i = 0; i < nq; ++i) {
+      out.points[i].j1 = j[3 * i];
+      out.points[i].j2 = j[3 * i + 1];
+      out.points[i].j3 = j[3 * i + 2];
+      // (stricter than PCL, which clears is_dense only for a row without neighbours)
+      if (std::isnan(j[3 * i]) || std::isnan(j[3 * i + 1]) || std::isnan(j[3 * i + 2])) out.is_dense = false;
+    }
+  }
+};
+
+// PrincipalCurvaturesEstimation<PointXYZRGB, Normal, PrincipalCurvatures> (evaluation.cpp:696-715): a
+// FeatureFromNormals, so Features<T>::compute's cast computes the surface normals for it.  With PCL
+// 1.7's indexing: computeFeature passes (*indices_)[i], an index into the *input*, to normals_, the
+// *surface's* normals.  So the query normal of row i is the normal of cloud point i, not the
+// keypoint's own: the facade passes normals[0 .. nq).  More input points than normals, which PCL
+// would read out of bounds, is an error here.
+template <typename PointInT, typename PointNT, typename PointOutT>
+class PrincipalCurvaturesEstimation : public FeatureFromNormals<PointInT, PointNT, PointOutT> {
+ public:
+  typedef std::shared_ptr<PrincipalCurvaturesEstimation<PointInT, PointNT, PointOutT> > Ptr;
+  PrincipalCurvaturesEstimation() { this->name_ = "PrincipalCurvaturesEstimation"; }
+
+ protected:
+  void computeFeature(PointCloud<PointOutT>& out) override {
+    const PointCloud<PointInT>& surf = this->surface();
+    const size_t nq = this->input_->size(), ns = surf.size();
+    if (!this->normals_ || this->normals_->size() != ns) {
+      PCL_ERROR("[pcl::PrincipalCurvaturesEstimation::compute] the input normals are missing or do not match the "
+                "search surface\n");
+      return;
+    }
+    if (nq > ns) {  // row i reads normals_[i]
+      PCL_ERROR("[pcl::PrincipalCurvaturesEstimation::compute] input index %zu is beyond the search surface "
+                "(%zu points)\n", ns, ns);
+      return;
+    }
+    const detail::SoA s = detail::soa_xyz(surf), q = detail::soa_xyz(*this->input_);
+    const detail::SoA nrm = detail::soa_normals(*this->normals_);
+    std::vector<float> pc(nq * 5);
+    // (the query normals are the first nq surface normals: the arrays' own prefixes)
+    if (!detail::ok(pfx_principal_curvatures(detail::context(), s.x.data(), s.y.data(), s.z.data(), nrm.x.data(),
+                                             nrm.y.data(), nrm.z.data(), (int64_t)ns, q.x.data(), q.y.data(),
+                                             q.z.data(), nrm.x.data(), nrm.y.data(), nrm.z.data(), (int64_t)nq,
+                                             this->search_radius_, pc.data()),
+                    "PrincipalCurvaturesEstimation"))
+      return;
+    out.resize(nq);
+    out.is_dense = true;
+    for (size_t i = 0; i < nq; ++i) {
+      for (int c = 0; c < 3; ++c) out.points[i].principal_curvature[c] = pc[5 * i + (size_t)c];
+      out.points[i].pc1 = pc[5 * i + 3];
+      out.points[i].pc2 = pc[5 * i + 4];
+      // (stricter than PCL, which clears is_dense only for a row without neighbours)
+      for (int c = 0; c < 5; ++c)
+        if (std::isnan(pc[5 * i + (size_t)c])) out.is_dense = false;
     }
   }
 };
@@ -1256,6 +1351,10 @@ template <> struct DescriptorLayout<PFHSignature125> { static constexpr int dim 
 template <int N> struct DescriptorLayout<Histogram<N> > { static constexpr int dim = N, stride = N; };
 // (DefaultPointRepresentation<IntensityGradient>: the three gradient floats of a 16-byte point)
 template <> struct DescriptorLayout<IntensityGradient> { static constexpr int dim = 3, stride = 4; };
+template <> struct DescriptorLayout<MomentInvariants> { static constexpr int dim = 3, stride = 3; };
+// (DefaultPointRepresentation caps a point type it does not know at its first three floats: the
+// principal direction alone is compared)
+template <> struct DescriptorLayout<PrincipalCurvatures> { static constexpr int dim = 3, stride = 5; };
 }  // namespace detail
 
 // KdTreeFLANN<FeatureT> with nearestKSearch(k = 1), as the reference uses it (features.h:258-272):

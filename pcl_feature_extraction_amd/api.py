@@ -311,6 +311,31 @@ class Context:
                                        _ptr(cx), _ptr(cy), _ptr(cz), nq, float(r), D, G, _ptr(out)))
         return out
 
+    def moment_invariants(self, sx, sy, sz, qx, qy, qz, r):
+        """MomentInvariantsEstimation (pfx_moment_invariants): (nq, 3) float32, j1 j2 j3 of the radius
+        neighbours of each query; a NaN row for a query without neighbours."""
+        sx, sy, sz, qx, qy, qz = map(_f32, (sx, sy, sz, qx, qy, qz))
+        nq = len(qx)
+        out = np.empty((nq, 3), dtype=np.float32)
+        self._check(self._lib.pfx_moment_invariants(self.h, _ptr(sx), _ptr(sy), _ptr(sz), len(sx), _ptr(qx), _ptr(qy),
+                                                    _ptr(qz), nq, float(r), _ptr(out)))
+        return out
+
+    def principal_curvatures(self, sx, sy, sz, snx, sny, snz, qx, qy, qz, qnx, qny, qnz, r):
+        """PrincipalCurvaturesEstimation (pfx_principal_curvatures): (nq, 5) float32, the principal
+        direction x y z, then pc1 and pc2.  (snx, sny, snz) are the surface normals, (qnx, qny, qnz)
+        the normal at each query; a NaN row for a query without neighbours."""
+        sx, sy, sz, snx, sny, snz, qx, qy, qz, qnx, qny, qnz = map(
+            _f32, (sx, sy, sz, snx, sny, snz, qx, qy, qz, qnx, qny, qnz))
+        if len(snx) != len(sx) or len(qnx) != len(qx):
+            raise ValueError("principal_curvatures: one normal per surface point and one per query")
+        nq = len(qx)
+        out = np.empty((nq, 5), dtype=np.float32)
+        self._check(self._lib.pfx_principal_curvatures(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(snx), _ptr(sny),
+                                                       _ptr(snz), len(sx), _ptr(qx), _ptr(qy), _ptr(qz), _ptr(qnx),
+                                                       _ptr(qny), _ptr(qnz), nq, float(r), _ptr(out)))
+        return out
+
     def shape_context(self, sx, sy, sz, nx, ny, nz, qx, qy, qz, r, min_radius=None, point_density_radius=None,
                       rnd=None):
         """ShapeContext3DEstimation (pfx_shape_context): desc (nq, 1980) and rf (nq, 9) float32.  The
@@ -544,6 +569,20 @@ class Context:
         self._check(self._lib.pfx_rift_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(sgx), _ptr(sgy), _ptr(sgz),
                                            sx.numel(), _ptr(cx), _ptr(cy), _ptr(cz), cx.numel(), float(r),
                                            int(nr_distance_bins), int(nr_gradient_bins), _ptr(out)))
+
+    def moment_invariants_dev(self, sx, sy, sz, qx, qy, qz, r, out):
+        """pfx_moment_invariants_dev: out is an (nq, 3) float32 device tensor; no host synchronisation
+        (a neighbourhood beyond capacity is reported by the next synchronize())."""
+        self._check(self._lib.pfx_moment_invariants_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), sx.numel(), _ptr(qx),
+                                                        _ptr(qy), _ptr(qz), qx.numel(), float(r), _ptr(out)))
+
+    def principal_curvatures_dev(self, sx, sy, sz, snx, sny, snz, qx, qy, qz, qnx, qny, qnz, r, out):
+        """pfx_principal_curvatures_dev: out is an (nq, 5) float32 device tensor; no host
+        synchronisation (a neighbourhood beyond capacity is reported by the next synchronize())."""
+        self._check(self._lib.pfx_principal_curvatures_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(snx), _ptr(sny),
+                                                           _ptr(snz), sx.numel(), _ptr(qx), _ptr(qy), _ptr(qz),
+                                                           _ptr(qnx), _ptr(qny), _ptr(qnz), qx.numel(), float(r),
+                                                           _ptr(out)))
 
     def shape_context_dev(self, sx, sy, sz, nx, ny, nz, qx, qy, qz, r, desc, rf, min_radius=None,
                           point_density_radius=None, rnd=None):

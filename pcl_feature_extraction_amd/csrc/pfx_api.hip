@@ -111,6 +111,7 @@ pfx_status pfx_ctx_create(int device, pfx_ctx** out) {
     ctx->stats["spin_chunk"] = pfx::spin_chunk();
     ctx->stats["rift_cap_small"] = pfx::rift_cap_small();
     ctx->stats["sc_cap_small"] = pfx::sc_cap_small();
+    ctx->stats["moments_cap_small"] = pfx::moments_cap_small();
     // grid builds by builder (pfx_grid.hip), and speculative counting builds that met a fat cell
     for (const char* s : {"grid_count_builds", "grid_sort_builds", "grid_hinted_sort_builds", "grid_fat_fallbacks"})
       ctx->stats[s] = 0;
@@ -147,6 +148,7 @@ void pfx_ctx_destroy(pfx_ctx* ctx) {
   if (ctx->spin_rb_mem) (void)hipHostFree(ctx->spin_rb_mem);
   if (ctx->rift_rb_mem) (void)hipHostFree(ctx->rift_rb_mem);
   if (ctx->sc_rb_mem) (void)hipHostFree(ctx->sc_rb_mem);
+  if (ctx->moments_rb_mem) (void)hipHostFree(ctx->moments_rb_mem);
   delete ctx;
 }
 
@@ -195,6 +197,7 @@ pfx_status pfx_ctx_trim(pfx_ctx* ctx) {
   pfx::spin_resolve(ctx);
   pfx::rift_resolve(ctx);
   pfx::sc_resolve(ctx);
+  pfx::moments_resolve(ctx);
   pfx::narf_release(ctx);
   pfx::normals_release(ctx);
   pfx::keypoints_release(ctx);
@@ -219,6 +222,7 @@ pfx_status pfx_ctx_synchronize(pfx_ctx* ctx) {
   pfx::spin_resolve(ctx);
   pfx::rift_resolve(ctx);
   pfx::sc_resolve(ctx);
+  pfx::moments_resolve(ctx);
   PFX_API_END(ctx)
 }
 
@@ -261,13 +265,14 @@ pfx_status pfx_ctx_last_stats(pfx_ctx* ctx, const char* what, int64_t* value) {
   PFX_API_BEGIN
   if (!ctx || !what || !value) throw Error(PFX_ERR_INVALID, "null argument");
   if (ctx->fpfh_pending || ctx->pfh_pending || ctx->spin_pending || ctx->igrad_pending || ctx->rift_pending ||
-      ctx->sc_pending || ctx->lrf_pending) {
+      ctx->sc_pending || ctx->lrf_pending || ctx->moments_pending || ctx->pcurv_pending) {
     PFX_HIP(hipStreamSynchronize(ctx->stream));
     pfx::fpfh_resolve(ctx);
     pfx::pfh_resolve(ctx);
     pfx::spin_resolve(ctx);
     pfx::rift_resolve(ctx);
     pfx::sc_resolve(ctx);
+    pfx::moments_resolve(ctx);
   }
   auto it = ctx->stats.find(what);
   if (it == ctx->stats.end()) throw Error(PFX_ERR_INVALID, std::string("unknown stat ") + what);
@@ -859,6 +864,98 @@ pfx_status pfx_rift(pfx_ctx* ctx, const float* sx, const float* sy, const float*
   if (nq) PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * S, hipMemcpyDeviceToHost, ctx->stream));
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   pfx::rift_resolve(ctx);  // the host API reports at once
+  PFX_API_END(ctx)
+}
+
+// every check that precedes a launch (host and device entry points alike)
+static void moments_check(const float* sx, const float* sy, const float* sz, int64_t n_surface, const float* qx,
+                          const float* qy, const float* qz, int64_t nq, double radius, const float* out) {
+  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!out || !qx || !qy || !qz)) ||
+      (n_surface && (!sx || !sy || !sz)))
+    throw Error(PFX_ERR_INVALID, "moment_invariants: invalid arguments");
+}
+
+pfx_status pfx_moment_invariants_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                                     int64_t n_surface, const float* d_qx, const float* d_qy, const float* d_qz,
+                                     int64_t nq, double radius, float* d_out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  moments_check(d_sx, d_sy, d_sz, n_surface, d_qx, d_qy, d_qz, nq, radius, d_out);
+  pfx::moments_dev(ctx, d_sx, d_sy, d_sz, n_surface, d_qx, d_qy, d_qz, nq, radius, d_out);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_moment_invariants(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t n_surface,
+                                 const float* qx, const float* qy, const float* qz, int64_t nq, double radius,
+                                 float* out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  moments_check(sx, sy, sz, n_surface, qx, qy, qz, nq, radius, out);
+  if (nq) {
+    float* dsx = stage_in(ctx, "in_x", sx, n_surface);
+    float* dsy = stage_in(ctx, "in_y", sy, n_surface);
+    float* dsz = stage_in(ctx, "in_z", sz, n_surface);
+    float* dqx = stage_in(ctx, "in_qx", qx, nq);
+    float* dqy = stage_in(ctx, "in_qy", qy, nq);
+    float* dqz = stage_in(ctx, "in_qz", qz, nq);
+    float* dout = ctx->buf("out_moments").as<float>(nq * 3 + 1);
+    pfx::moments_dev(ctx, dsx, dsy, dsz, n_surface, dqx, dqy, dqz, nq, radius, dout);
+    PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * 3, hipMemcpyDeviceToHost, ctx->stream));
+    PFX_HIP(hipStreamSynchronize(ctx->stream));
+    pfx::moments_resolve(ctx);  // the host API reports at once
+  }
+  PFX_API_END(ctx)
+}
+
+static void pcurv_check(const float* sx, const float* sy, const float* sz, const float* snx, const float* sny,
+                        const float* snz, int64_t n_surface, const float* qx, const float* qy, const float* qz,
+                        const float* qnx, const float* qny, const float* qnz, int64_t nq, double radius,
+                        const float* out) {
+  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!out || !qx || !qy || !qz || !qnx || !qny || !qnz)) ||
+      (n_surface && (!sx || !sy || !sz || !snx || !sny || !snz)))
+    throw Error(PFX_ERR_INVALID, "principal_curvatures: invalid arguments");
+}
+
+pfx_status pfx_principal_curvatures_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                                        const float* d_snx, const float* d_sny, const float* d_snz,
+                                        int64_t n_surface, const float* d_qx, const float* d_qy, const float* d_qz,
+                                        const float* d_qnx, const float* d_qny, const float* d_qnz, int64_t nq,
+                                        double radius, float* d_out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  pcurv_check(d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, d_qnx, d_qny, d_qnz, nq, radius,
+              d_out);
+  pfx::pcurv_dev(ctx, d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, d_qnx, d_qny, d_qnz, nq,
+                 radius, d_out);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_principal_curvatures(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz,
+                                    const float* snx, const float* sny, const float* snz, int64_t n_surface,
+                                    const float* qx, const float* qy, const float* qz, const float* qnx,
+                                    const float* qny, const float* qnz, int64_t nq, double radius, float* out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  pcurv_check(sx, sy, sz, snx, sny, snz, n_surface, qx, qy, qz, qnx, qny, qnz, nq, radius, out);
+  if (nq) {
+    float* dsx = stage_in(ctx, "in_x", sx, n_surface);
+    float* dsy = stage_in(ctx, "in_y", sy, n_surface);
+    float* dsz = stage_in(ctx, "in_z", sz, n_surface);
+    float* dnx = stage_in(ctx, "in_nx", snx, n_surface);
+    float* dny = stage_in(ctx, "in_ny", sny, n_surface);
+    float* dnz = stage_in(ctx, "in_nz", snz, n_surface);
+    float* dqx = stage_in(ctx, "in_qx", qx, nq);
+    float* dqy = stage_in(ctx, "in_qy", qy, nq);
+    float* dqz = stage_in(ctx, "in_qz", qz, nq);
+    float* dax = stage_in(ctx, "in_qnx", qnx, nq);
+    float* day = stage_in(ctx, "in_qny", qny, nq);
+    float* daz = stage_in(ctx, "in_qnz", qnz, nq);
+    float* dout = ctx->buf("out_pcurv").as<float>(nq * 5 + 1);
+    pfx::pcurv_dev(ctx, dsx, dsy, dsz, dnx, dny, dnz, n_surface, dqx, dqy, dqz, dax, day, daz, nq, radius, dout);
+    PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * 5, hipMemcpyDeviceToHost, ctx->stream));
+    PFX_HIP(hipStreamSynchronize(ctx->stream));
+    pfx::moments_resolve(ctx);  // the host API reports at once
+  }
   PFX_API_END(ctx)
 }
 

@@ -192,6 +192,9 @@ struct pfx_ctx {
   // sc_dev's and shot_lrf_dev's, the same way (pfx::sc_resolve)
   void* sc_rb_mem = nullptr;
   bool sc_pending = false, lrf_pending = false;
+  // moments_dev's and pcurv_dev's, the same way (pfx::moments_resolve)
+  void* moments_rb_mem = nullptr;
+  bool moments_pending = false, pcurv_pending = false;
   int64_t sc_rnd_n = 0;  // floats of the default random stream held in buf("sc_rnd")
   // one side stream + fork/join events (normal estimation's long-list chains), created on first use
   hipStream_t side = nullptr;
@@ -402,6 +405,15 @@ void shot_lrf_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* s
                   const float* qy, const float* qz, int64_t nq, double r, float* rf);
 void sc_resolve(pfx_ctx* ctx);
 int sc_cap_small();  // neighbours of the first pass (stat "sc_cap_small")
+// moment invariants and principal curvatures (pfx_moments.hip): stream-ordered, no host
+// synchronisation; errors and statistics as spin images (moments_resolve serves both)
+void moments_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, const float* qx,
+                 const float* qy, const float* qz, int64_t nq, double r, float* out);
+void pcurv_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx, const float* sny,
+               const float* snz, int64_t ns, const float* qx, const float* qy, const float* qz, const float* qnx,
+               const float* qny, const float* qnz, int64_t nq, double r, float* out);
+void moments_resolve(pfx_ctx* ctx);
+int moments_cap_small();  // neighbours of the first pass (stat "moments_cap_small")
 // boost::mt19937 through uniform_01<float>: n floats of the stream of `seed` after `skip` floats
 void rng_uniform01(uint32_t seed, int64_t skip, int64_t n, float* out);
 void range_image_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
