@@ -360,10 +360,15 @@ void points_bbox(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, cons
   bbox_dev(ctx, g, d_x, d_y, d_z, n, lo, hi);
 }
 
+// fork_gather (the normal estimation's opt-in, honoured by hinted radix builds only): the sorted
+// coordinates are gathered on the context's side stream while the cell starts are completed here;
+// the caller owes ctx->join_side() before anything reads sx / sy / sz / sp (nothing between the
+// sort and the list kernels does: the list set-up reads cell_start and skeys).
 void build_grid(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const float* d_z,
-                int64_t n, double radius, bool use_hint) {
+                int64_t n, double radius, bool use_hint, bool fork_gather) {
   PFX_CHECK(n >= 0 && n < (int64_t(1) << 31), "point count must be in [0, 2^31)");
   PFX_CHECK(radius > 0.0, "radius must be > 0");
+  ctx->join_side(ctx->stream);  // (a gather still forked would write into this build's arrays)
   if (&g == &ctx->grid_b) {  // a grid prepared ahead for the next fpfh_dev no longer holds
     ctx->prep_x = nullptr;
     ctx->prep_n = -1;
@@ -497,12 +502,18 @@ void build_grid(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const
       check_launch("k_cell_keys");
       PFX_HIP(rocprim::radix_sort_pairs<SortCfg>(tmp, sort_bytes, keys, keys2, vals,
                                         reinterpret_cast<uint32_t*>(g.perm), (size_t)n, 0, bits, st));
+      const bool forked = fork_gather && g.oob != nullptr;
+      if (forked) ctx->fork_side(st);
+      const auto gather = [&](hipStream_t s) {
+        k_gather_sorted<<<(unsigned)ceil_div(n, 256), 256, 0, s>>>(d_x, d_y, d_z, n, reinterpret_cast<uint32_t*>(g.perm),
+                                                                   g.sx, g.sy, g.sz, g.sp);
+        check_launch("k_gather_sorted");
+      };
+      if (forked) gather(ctx->side);
       k_mark_starts<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(keys2, n, g.cell_start);
       auto r = rocprim::make_reverse_iterator(g.cell_start + C + 1);
       PFX_HIP(rocprim::inclusive_scan(tmp, scan_bytes, r, r, (size_t)(C + 1), rocprim::minimum<int32_t>(), st));
-      k_gather_sorted<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(
-          d_x, d_y, d_z, n, reinterpret_cast<uint32_t*>(g.perm), g.sx, g.sy, g.sz, g.sp);
-      check_launch("k_gather_sorted");
+      if (!forked) gather(st);
     }
   }
   if (!g.oob && n > 0 && g.hint_user) {

@@ -221,6 +221,25 @@ struct pfx_ctx {
     PFX_HIP(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, prio));
     for (auto& e : fork_ev) PFX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
+  // The normal estimation's hinted grid build may leave its coordinate gather (and the caller the
+  // NaN fill of the outputs) on the side stream, off the chain that leads to the list kernels
+  // (build_grid with fork_gather): fork_side() orders the side stream behind `st`, join_side()
+  // orders `st` behind whatever was put there since.  The join comes before the first kernel that
+  // reads the sorted coordinates (build_lists, before the list kernels) and, as a guard, at the
+  // start of the next grid build and of a context synchronisation.
+  bool side_pending = false;
+  void fork_side(hipStream_t st) {
+    ensure_side();
+    PFX_HIP(hipEventRecord(fork_ev[0], st));
+    PFX_HIP(hipStreamWaitEvent(side, fork_ev[0], 0));
+    side_pending = true;
+  }
+  void join_side(hipStream_t st) {
+    if (!side_pending) return;
+    side_pending = false;
+    PFX_HIP(hipEventRecord(fork_ev[1], side));
+    PFX_HIP(hipStreamWaitEvent(st, fork_ev[1], 0));
+  }
   // small pinned host block for the per-call readbacks (counters, cursors): one D2H copy of
   // pinned memory per synchronisation instead of staged pageable copies
   void* host_rb = nullptr;
@@ -277,7 +296,7 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // grid building (pfx_grid.hip)
 void build_grid(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const float* d_z,
-                int64_t n, double radius, bool use_hint = false);
+                int64_t n, double radius, bool use_hint = false, bool fork_gather = false);
 // bounding box of the finite points (0 when there are none), synchronous
 void points_bbox(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const float* d_z, int64_t n,
                  double lo[3], double hi[3]);

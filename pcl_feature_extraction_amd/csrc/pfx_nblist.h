@@ -75,6 +75,8 @@ struct NormalsState {
   uint64_t grid_gen = 0;  // grid_a's build that indexes (x, y, z, n, r) (pfx_normals_prepare_dev)
   // normals_launch_dev: the lists check still owed by normals_finish_dev, and the outputs to redo
   bool pending = false;
+  // the chains' counters were cleared ahead of the list kernels (normals_speculative_lists)
+  bool nlong_zeroed = false;
   // normals_grid_launch_dev: grid_a build `grid_ahead_gen` queued for (x, n, r); 0: none
   uint64_t grid_ahead_gen = 0;
   const float *grid_ahead_x = nullptr, *grid_ahead_y = nullptr, *grid_ahead_z = nullptr;

@@ -283,101 +283,166 @@ __global__ void __launch_bounds__(256) k_tile_class(GridView g, const int32_t* _
 }
 
 // Unmasked builds: the queries are the finite points in cell order, so the tiles are the 16-query
-// chunks of each cell and cell_start states them outright.  A thread takes kCellsPerThread
-// consecutive cells: block_runs and the class once per cell (k_tile_class: once per tile), the
-// workgroup's tiles per class summed in LDS and reserved with one atomic per class and workgroup
-// (one per wave and class made ~15,000 same-address atomics on the 1M-point room, whose occupied
-// cells are spread thinly over 3M: 229 us), then each cell's ceil(m / 16) records, in the same
-// regions.  Slots follow the cells inside a workgroup, so the records stay roughly in cell order
-// as before.  A cell above kCoopTiles tiles is written by the whole wave, so no lane is left
-// alone with a very full cell.
-constexpr int kCoopTiles = 16;
-constexpr int kCellsPerThread = 8;
-constexpr int64_t kCellsMinGrid = int64_t(256) * 256 * kCellsPerThread;  // cells that give every CU a workgroup
+// chunks of each cell and cell_start states them outright.  The kernel walks the sorted positions,
+// not the cells (the 1M-point room has ~17k occupied cells among 3M): a workgroup takes the slice
+// of kSlice consecutive positions and works in three steps between plain barriers.
+//  1. Position i starts a cell when skeys[i] < ncells and the key differs from skeys[i - 1]; the
+//     slice's cell starts are compacted in LDS in position order (a cell belongs to the slice its
+//     first point is in, however far it reaches).
+//  2. A thread per cell start: the point count from cell_start, block_runs and the class; the
+//     exclusive prefixes of the tile counts, over all cells and per class, and one reservation per
+//     class and workgroup (one per wave and class made ~15,000 same-address atomics on the room,
+//     229 us; one per class and 2048 cells still ~5,800 from 1,465 workgroups).
+//  3. The records, kRunCells cells at a time: their runs staged in LDS, then 256 tiles at a time a
+//     thread per tile finds its cell and slot, and the threads spread over (tile, word), so a
+//     record's 24 words leave as one 96-byte run whatever the cell's tile count (no lane writes a
+//     cell's tiles one after the other).
+// Slots follow the cells inside a workgroup and the slices are contiguous, so the records stay
+// roughly in cell order, in the same regions as k_tile_class's.  The cost follows the points and
+// tiles, not the grid's cell count.
+constexpr int kSlicePerThread = 16;
+constexpr int kSlice = 256 * kSlicePerThread;  // positions per workgroup
+constexpr int kRunCells = 128;                 // cells whose runs are staged per round of step 3
 __device__ __forceinline__ int tile_class(int T) {
   // 3: small tiles (<= kTcapSmall candidates), 0: sparse, 1: dense, 2: wide (as k_tile_class)
   return T <= kTcapSmall ? 3 : (T <= kTcapSparse ? 0 : (T <= kTcapDense ? 1 : 2));
 }
-__global__ void __launch_bounds__(256) k_tile_cells(GridView g, int64_t ncells, int32_t* __restrict__ recs, int64_t n,
-                                                    int32_t* __restrict__ wide, int* __restrict__ counts) {
-  __shared__ int s_wave[4][4];  // [class][wave] tiles
+__device__ __forceinline__ void runs_store(int32_t* __restrict__ o, const Runs& R) {  // a record's words [0, kRecQ0)
+#pragma unroll
+  for (int r = 0; r < 9; ++r) o[r] = R.start[r];
+#pragma unroll
+  for (int r = 0; r < 10; ++r) o[9 + r] = R.pref[r];
+}
+__global__ void __launch_bounds__(256) k_tile_cells(GridView g, const uint32_t* __restrict__ skeys, int64_t ncells,
+                                                    int32_t* __restrict__ recs, int64_t n, int32_t* __restrict__ wide,
+                                                    int* __restrict__ counts) {
+  __shared__ int32_t s_pos[kSlice + 1];   // first position of the slice's c-th cell; [cells]: the last one's end
+  __shared__ int32_t s_tile[kSlice + 1];  // tiles of the slice's cells before c (every class)
+  __shared__ int32_t s_slot[kSlice];      // class << 30 | tiles of that class before c
+  __shared__ int32_t s_runs[kRunCells][kRecQ0];
+  __shared__ int32_t s_tat[256], s_tcell[256], s_tq0[256], s_tqn[256];  // step 3, per tile of a chunk
+  __shared__ int s_wave[5][4];  // [class, 4 = all][wave]
   __shared__ int s_base[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t c0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) * kCellsPerThread;
-  int32_t st[kCellsPerThread + 1];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  // step 1
+  const int64_t i0 = blockIdx.x * (int64_t)kSlice + (int64_t)tid * kSlicePerThread;
+  uint32_t key[kSlicePerThread];
+  if (i0 + kSlicePerThread <= n) {
+    const uint4* k4 = reinterpret_cast<const uint4*>(skeys + i0);  // (i0 is a multiple of 16)
 #pragma unroll
-  for (int j = 0; j <= kCellsPerThread; ++j) st[j] = g.cell_start[c0 + j <= ncells ? c0 + j : ncells];
-  // pass 1: tiles per class of this thread's cells
-  int cnt[4] = {0, 0, 0, 0};
-  unsigned cls_bits = 0;
+    for (int j = 0; j < kSlicePerThread / 4; ++j) {
+      const uint4 v = k4[j];
+      key[4 * j] = v.x; key[4 * j + 1] = v.y; key[4 * j + 2] = v.z; key[4 * j + 3] = v.w;
+    }
+  } else {
 #pragma unroll
-  for (int j = 0; j < kCellsPerThread; ++j) {
-    const int m = st[j + 1] - st[j];
-    if (m > 0) {  // (cells past the grid's end repeat cell_start[ncells]: empty)
+    for (int j = 0; j < kSlicePerThread; ++j) key[j] = i0 + j < n ? skeys[i0 + j] : 0xffffffffu;
+  }
+  uint32_t prev = (i0 > 0 && i0 < n) ? skeys[i0 - 1] : 0xffffffffu;  // (no cell has this key: < 2^26 cells)
+  unsigned starts = 0;
+#pragma unroll
+  for (int j = 0; j < kSlicePerThread; ++j) {
+    starts |= ((uint64_t)key[j] < (uint64_t)ncells && key[j] != prev) ? 1u << j : 0u;
+    prev = key[j];
+  }
+  {
+    const int mine = __popc(starts), incl = wave_incl_scan(mine);
+    if (lane == 63) s_wave[4][wv] = incl;
+    __syncthreads();
+    int at = incl - mine;
+    for (int w = 0; w < wv; ++w) at += s_wave[4][w];
+#pragma unroll
+    for (int j = 0; j < kSlicePerThread; ++j)
+      if (starts >> j & 1u) s_pos[at++] = (int32_t)(i0 + j);
+  }
+  const int cells = s_wave[4][0] + s_wave[4][1] + s_wave[4][2] + s_wave[4][3];
+  __syncthreads();
+  if (cells == 0) return;
+  // step 2 (every lane stays in the scans)
+  int before[5] = {0, 0, 0, 0, 0};  // tiles of the rounds so far: [class], [4] all
+  for (int c0 = 0; c0 < cells; c0 += 256) {
+    const int c = c0 + tid;
+    int nt = 0, cls = 0;
+    if (c < cells) {
+      const int32_t pos = s_pos[c];
+      const uint32_t k = skeys[pos];
+      const int32_t end = g.cell_start[(int64_t)k + 1];
+      if (c == cells - 1) s_pos[cells] = end;
+      nt = (end - pos + kQ - 1) / kQ;
       Runs R;
-      const int cls = tile_class(block_runs(g, (uint32_t)(c0 + j), R));
-      cls_bits |= (unsigned)cls << (2 * j);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) cnt[k] += cls == k ? (m + kQ - 1) / kQ : 0;
+      cls = tile_class(block_runs(g, k, R));
+      if (c < kRunCells) runs_store(s_runs[c], R);  // step 3's first round (the room: ~70 cells per slice)
     }
-  }
-  int first[4];
+    int ex[5];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int incl = wave_incl_scan(cnt[k]);
-    first[k] = incl - cnt[k];
-    if (lane == 63) s_wave[k][wv] = incl;
+    for (int k = 0; k < 5; ++k) {
+      const int v = (k == 4 || cls == k) ? nt : 0, incl = wave_incl_scan(v);
+      ex[k] = incl - v;
+      if (lane == 63) s_wave[k][wv] = incl;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      ex[k] += before[k];
+      for (int w = 0; w < 4; ++w) {
+        ex[k] += w < wv ? s_wave[k][w] : 0;
+        before[k] += s_wave[k][w];
+      }
+    }
+    if (c < cells) {
+      s_tile[c] = ex[4];
+      s_slot[c] = (int32_t)((uint32_t)cls << 30) | (cls == 3 ? ex[3] : (cls == 2 ? ex[2] : (cls == 1 ? ex[1] : ex[0])));
+    }
+    __syncthreads();
+  }
+  if (tid == 0) s_tile[cells] = before[4];
+  if (tid < 4) {
+    const int ci = tid == 3 ? kTilesSmall : (tid == 2 ? kTilesWide : (tid == 1 ? kTilesDense : kTilesSparse));
+    const int total = tid == 3 ? before[3] : (tid == 2 ? before[2] : (tid == 1 ? before[1] : before[0]));
+    s_base[tid] = total ? atomicAdd(&counts[ci], total) : 0;
   }
   __syncthreads();
-  if (threadIdx.x < 4) {
-    const int k = threadIdx.x;
-    const int total = s_wave[k][0] + s_wave[k][1] + s_wave[k][2] + s_wave[k][3];
-    const int ci = k == 3 ? kTilesSmall : (k == 2 ? kTilesWide : (k == 1 ? kTilesDense : kTilesSparse));
-    s_base[k] = total ? atomicAdd(&counts[ci], total) : 0;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    first[k] += s_base[k];
-    for (int w = 0; w < wv; ++w) first[k] += s_wave[k][w];
-  }
-  // pass 2: the records (every lane of the wave stays in the loop)
-  auto emit = [&](const Runs& Rc, int k, int slot, int32_t q0, int qn) {
-    // small at [0, n) upward, wide at [0, n) downward from n - 1
-    const int64_t at = k == 3 ? slot : (k == 0 ? n + slot : (k == 1 ? 2 * n - 1 - slot : n - 1 - slot));
-    rec_write(recs + at * kRecInts, Rc, q0, qn);
-    if (k == 2) wide[slot] = (int32_t)at;
-  };
-#pragma unroll  // (st[] stays in registers)
-  for (int j = 0; j < kCellsPerThread; ++j) {
-    const int32_t s = st[j], m = st[j + 1] - st[j];
-    const int nt = (m + kQ - 1) / kQ, cls = (int)((cls_bits >> (2 * j)) & 3u);
-    Runs R;
-#pragma unroll
-    for (int r = 0; r < 9; ++r) R.start[r] = 0;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) R.pref[r] = 0;
-    int slot = 0;
-    if (m > 0) {
-      block_runs(g, (uint32_t)(c0 + j), R);
-      slot = cls == 3 ? first[3] : (cls == 2 ? first[2] : (cls == 1 ? first[1] : first[0]));
-#pragma unroll
-      for (int k = 0; k < 4; ++k) first[k] += cls == k ? nt : 0;
-      if (nt <= kCoopTiles)
-        for (int i = 0; i < nt; ++i) emit(R, cls, slot + i, s + kQ * i, min(kQ, m - kQ * i));
+  // step 3
+  for (int c0 = 0; c0 < cells; c0 += kRunCells) {
+    const int c1 = min(cells, c0 + kRunCells);
+    if (c0 > 0 && tid < c1 - c0) {  // (step 2 left the runs of the first kRunCells cells)
+      Runs R;
+      block_runs(g, skeys[s_pos[c0 + tid]], R);
+      runs_store(s_runs[tid], R);
     }
-    uint64_t big = __ballot(m > 0 && nt > kCoopTiles);
-    while (big) {
-      const int l = __builtin_ctzll(big);
-      big &= big - 1;
-      Runs Rl;
-#pragma unroll
-      for (int r = 0; r < 9; ++r) Rl.start[r] = __shfl(R.start[r], l);
-#pragma unroll
-      for (int r = 0; r < 10; ++r) Rl.pref[r] = __shfl(R.pref[r], l);
-      const int32_t sl = __shfl(s, l), ml = __shfl(m, l);
-      const int fl = __shfl(slot, l), ntl = __shfl(nt, l), kl = __shfl(cls, l);
-      for (int i = lane; i < ntl; i += 64) emit(Rl, kl, fl + i, sl + kQ * i, min(kQ, ml - kQ * i));
+    __syncthreads();
+    const int t1 = s_tile[c1];
+    for (int tb = s_tile[c0]; tb < t1; tb += 256) {
+      // a thread per tile: its cell (the last c with s_tile[c] <= t: every cell has a tile), record
+      // slot, first query and query count, found once for the record's 24 words
+      const int nt = min(256, t1 - tb);
+      if (tid < nt) {
+        const int t = tb + tid;
+        int lo = c0, hi = c1 - 1;
+        while (lo < hi) {
+          const int mid = (lo + hi + 1) >> 1;
+          if (s_tile[mid] <= t) lo = mid; else hi = mid - 1;
+        }
+        const int ti = t - s_tile[lo], k = (int)((uint32_t)s_slot[lo] >> 30);
+        const int slot = s_base[k] + (s_slot[lo] & 0x3fffffff) + ti;
+        const int32_t pos = s_pos[lo], m = s_pos[lo + 1] - pos;
+        // small at [0, n) upward, wide at [0, n) downward from n - 1 (at < 2n < 2^29)
+        const int64_t at = k == 3 ? slot : (k == 0 ? n + slot : (k == 1 ? 2 * n - 1 - slot : n - 1 - slot));
+        s_tat[tid] = (int32_t)at;
+        s_tcell[tid] = lo - c0;
+        s_tq0[tid] = pos + kQ * ti;
+        s_tqn[tid] = min(kQ, m - kQ * ti);
+        if (k == 2) wide[slot] = (int32_t)at;
+      }
+      __syncthreads();
+      const int words = nt * kRecInts;
+#pragma unroll 4
+      for (int idx = tid; idx < words; idx += 256) {
+        const int tl = idx / kRecInts, w = idx - tl * kRecInts;
+        const int32_t v = w < kRecQ0 ? s_runs[s_tcell[tl]][w] : (w == kRecQ0 ? s_tq0[tl] : (w == kRecQn ? s_tqn[tl] : 0));
+        recs[(int64_t)s_tat[tl] * kRecInts + w] = v;
+      }
+      __syncthreads();
     }
   }
 }
@@ -1845,20 +1910,16 @@ struct ListBuild {
       // every finite point, in cell order: sorted positions [0, cell_start[ncells])
       k_list_init<<<nb, 256, 0, st>>>(qpos, n, G.cell_start + G.ncells, d_nq, counters, kNCounters, cursor, tq,
                                       tq_dev);
-      // tiles from the cells: one launch over the cells instead of the five over the queries
-      // below.  By default only where that launch fills the chip and the grid is not mostly empty
-      // cells: at least 256 CUs x 2048 cells per workgroup, at most 4 cells per point (1M-point
-      // room, 3M cells: 212.9 against 210.5 Mpoints/s mean of five; configs[1], 170k cells in 83
-      // workgroups: 47.6 against 48.1).  PFX_LIST_SETUP=scan|cells forces either (A/B runs, tests).
+      // tiles from the cells: one launch over the sorted positions instead of the five over the
+      // queries below.  Its cost follows the points, not the grid's cells, so it is the default of
+      // every unmasked build (the kernel it replaced walked the cells and was kept to grids of
+      // >= 2^19 cells and <= 4 cells per point; DESIGN section 9 has the A/B of both rules).
+      // PFX_LIST_SETUP=scan|cells forces either (A/B runs, tests).
       const char* mode = std::getenv("PFX_LIST_SETUP");
-      const bool cells = mode && std::strcmp(mode, "cells") == 0
-                             ? true
-                             : (mode && std::strcmp(mode, "scan") == 0
-                                    ? false
-                                    : G.ncells >= kCellsMinGrid && G.ncells <= std::max<int64_t>(4 * n, kCellsMinGrid));
+      const bool cells = !(mode && std::strcmp(mode, "scan") == 0);
       ++ctx->stats[std::string(tag) + (cells ? "_setup_cells" : "_setup_scan")];
       if (cells) {
-        k_tile_cells<<<(unsigned)ceil_div(G.ncells, 256 * kCellsPerThread), 256, 0, st>>>(g, G.ncells, recs, n, wq, counters);
+        k_tile_cells<<<(unsigned)ceil_div(n, kSlice), 256, 0, st>>>(g, G.skeys, G.ncells, recs, n, wq, counters);
         check_launch("nblist cell tiles");
         return;
       }
@@ -2042,6 +2103,7 @@ void build_lists(pfx_ctx* ctx, const Grid& G, const uint8_t* mask, double radius
     throw Error(PFX_ERR_CAPACITY, std::string(tag) + ": neighbour lists support < 2^28 points");
   ListBuild b(ctx, G, tag, radius, sorted, compact);
   b.setup(mask, want);
+  ctx->join_side(b.st);  // a forked coordinate gather (build_grid): the list kernels are its first readers
   if (gate && ctx->lists_gate) {  // pfx_normals_gate_dev: the caller's event, once, right before the list kernels
     // (after the list set-up above, which therefore overlaps the gated stage)
     PFX_HIP(hipStreamWaitEvent(b.st, ctx->lists_gate, 0));

@@ -44,6 +44,8 @@ static_assert(kLaneMax >= kLaneMaxCompact, "lists up to kLaneMaxCompact must tak
 #define PFX_LANE_DENSE_MUL 2
 #endif
 constexpr int kLaneMaxDense = PFX_LANE_DENSE_MUL * kLaneMax;
+// the chains' device counters: [0] long lists, [1..3] chain modes (staged, table, lane), [4] deferred workgroups
+constexpr int kNLong = 5;
 
 __device__ __forceinline__ void chain_add(float a[9], float x, float y, float z) {
   a[0] = a[0] + x * x;
@@ -513,9 +515,11 @@ struct LongLds {
 
 // NaN (PCL's value for points without a normal: std::numeric_limits<float>::quiet_NaN(),
 // 0x7FC00000, the bits finish_normal writes too) in the four output arrays, one launch
+// (zero[0, nzero): small counters of the caller's cleared by the same launch, nullable)
 __global__ void k_nan_fill4(float* __restrict__ a, float* __restrict__ b, float* __restrict__ c,
-                            float* __restrict__ d, int64_t n) {
+                            float* __restrict__ d, int64_t n, int* __restrict__ zero, int nzero) {
   const float v = __builtin_nanf("");
+  if (blockIdx.x == 0 && (int)threadIdx.x < nzero) zero[threadIdx.x] = 0;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     a[i] = v; b[i] = v; c[i] = v; d[i] = v;
   }
@@ -730,6 +734,7 @@ void normals_lists_dev(pfx_ctx* ctx, const float* x, const float* y, const float
   ns.z = z;
   ns.r = r;
   ns.L = NbLists();
+  ns.nlong_zeroed = false;
   if (n == 0) {
     ns.ready = true;
     return;
@@ -737,7 +742,7 @@ void normals_lists_dev(pfx_ctx* ctx, const float* x, const float* y, const float
   hipStream_t st = ctx->stream;
   TimeScope total(ctx, "normals_lists_phase", true);
   build_grid(ctx, ctx->grid_a, x, y, z, n, r);
-  k_nan_fill4<<<(unsigned)std::min<int64_t>(ceil_div(n, 256), 4096), 256, 0, st>>>(nx, ny, nz, curv, n);
+  k_nan_fill4<<<(unsigned)std::min<int64_t>(ceil_div(n, 256), 4096), 256, 0, st>>>(nx, ny, nz, curv, n, nullptr, 0);
   check_launch("k_nan_fill4");
   build_lists(ctx, ctx->grid_a, nullptr, r, true, ns.L, "normals", false, 1, false, /*gate=*/true);
   ctx->stats["normals_neighbors"] = ns.L.total;
@@ -760,8 +765,12 @@ void normals_chains_dev(pfx_ctx* ctx, pfx_ctx* owner, const uint8_t* mask, int w
   const Grid& G = owner->grid_a;
   int32_t* longq = ctx->buf("normals_longq").as<int32_t>(L.nq);
   // [0] long lists, [1..3] chain modes (staged, table, lane), [4] deferred workgroups
-  int* n_long = ctx->buf("normals_nlong").as<int>(5);
-  PFX_HIP(hipMemsetAsync(n_long, 0, 5 * sizeof(int), st));
+  int* n_long = ctx->buf("normals_nlong").as<int>(kNLong);
+  // (a speculative estimation cleared them with its NaN fill, ahead of the list kernels: the fill
+  // launches of a 20-byte memset otherwise sit between the lists and the chains)
+  NormalsState& own = *owner->normals;
+  if (!(ctx == owner && own.nlong_zeroed)) PFX_HIP(hipMemsetAsync(n_long, 0, kNLong * sizeof(int), st));
+  own.nlong_zeroed = false;
   const int64_t nb = ceil_div(L.nq, 256);
   // the long lists first: when they are few (their chains, bound by the longest list, leave the
   // device mostly idle) k_normals_long runs on a side stream concurrently with the short-list
@@ -881,9 +890,30 @@ bool normals_speculative_lists(pfx_ctx* ctx, const float* x, const float* y, con
   const bool ahead = ns.grid_ahead_gen != 0 && ns.grid_ahead_gen == ctx->grid_a.gen && ns.grid_ahead_x == x &&
                      ns.grid_ahead_y == y && ns.grid_ahead_z == z && ns.grid_ahead_n == n && ns.grid_ahead_r == r;
   ns.grid_ahead_gen = 0;
-  if (!ahead) build_grid(ctx, ctx->grid_a, x, y, z, n, r, /*use_hint=*/true);
-  k_nan_fill4<<<(unsigned)std::min<int64_t>(ceil_div(n, 256), 4096), 256, 0, ctx->stream>>>(nx, ny, nz, curv, n);
+  // The chain to the first list kernel is a row of small dependent launches with the device nearly
+  // idle, and two of them feed nothing in it: the coordinate gather (first read by the list
+  // kernels) and the NaN fill of the outputs (first touched by the chains).  Both go to the side
+  // stream, forked after the sort and joined by build_lists before the list kernels.
+  // PFX_GATHER_FORK=0 keeps them in line (A/B runs, tests).
+  struct SideJoin {  // whichever way this ends, nothing stays forked
+    pfx_ctx* ctx;
+    ~SideJoin() {
+      try {
+        ctx->join_side(ctx->stream);
+      } catch (...) {
+      }
+    }
+  } side_join{ctx};
+  const char* fork_env = std::getenv("PFX_GATHER_FORK");
+  const bool fork_gather = !(fork_env && std::strcmp(fork_env, "0") == 0);
+  if (!ahead) build_grid(ctx, ctx->grid_a, x, y, z, n, r, /*use_hint=*/true, fork_gather);
+  ctx->stats["normals_gather_forked"] += ctx->side_pending ? 1 : 0;
+  // (the chains' counters too: their own fill launches sat between the lists and the chains)
+  int* n_long = ctx->buf("normals_nlong").as<int>(kNLong);
+  k_nan_fill4<<<(unsigned)std::min<int64_t>(ceil_div(n, 256), 4096), 256, 0,
+                ctx->side_pending ? ctx->side : ctx->stream>>>(nx, ny, nz, curv, n, n_long, kNLong);
   check_launch("k_nan_fill4");
+  ns.nlong_zeroed = true;
   build_lists(ctx, ctx->grid_a, nullptr, r, true, ns.L, "normals", /*defer=*/true, /*want=*/1, /*compact=*/true,
               /*gate=*/true);
   return true;
