@@ -36,10 +36,27 @@ void harvest_timing(pfx_ctx* ctx) {
   ctx->timer.pending.clear();
 }
 
-float* stage_in(pfx_ctx* ctx, const char* name, const float* host, int64_t count) {
-  float* d = ctx->buf(name).as<float>(count > 0 ? count : 1);
+float* stage_in(pfx_ctx* ctx, const std::string& name, const float* host, int64_t count) {
+  float* d = ctx->bufs[name].as<float>(count > 0 ? count : 1);
   if (count > 0) PFX_HIP(hipMemcpyAsync(d, host, sizeof(float) * count, hipMemcpyHostToDevice, ctx->stream));
   return d;
+}
+
+// A coordinate triple staged under a name stem: "in_" -> in_x in_y in_z (the surface), "in_n" ->
+// in_nx .. (its normals, or RIFT's gradients), "in_q" -> in_qx .. (the queries), "in_qn" -> in_qnx ..
+// (their normals or axes).
+struct Dev3 {
+  float *x, *y, *z;
+};
+Dev3 stage3(pfx_ctx* ctx, const std::string& stem, const float* x, const float* y, const float* z, int64_t count) {
+  return Dev3{stage_in(ctx, stem + "x", x, count), stage_in(ctx, stem + "y", y, count),
+              stage_in(ctx, stem + "z", z, count)};
+}
+
+// nq rows of `width` elements back to the host, in stream order (host nullable: not wanted)
+template <class T>
+void rows_out(pfx_ctx* ctx, T* host, const T* dev, int64_t nq, int64_t width) {
+  if (nq && host) PFX_HIP(hipMemcpyAsync(host, dev, sizeof(T) * nq * width, hipMemcpyDeviceToHost, ctx->stream));
 }
 
 void check_ctx(pfx_ctx* ctx) {
@@ -143,12 +160,7 @@ void pfx_ctx_destroy(pfx_ctx* ctx) {
   if (ctx->spin_ev) (void)hipEventDestroy(ctx->spin_ev);
   if (ctx->host_rb) (void)hipHostFree(ctx->host_rb);
   if (ctx->host_scratch) (void)hipHostFree(ctx->host_scratch);
-  if (ctx->fpfh_rb_mem) (void)hipHostFree(ctx->fpfh_rb_mem);
-  if (ctx->pfh_rb_mem) (void)hipHostFree(ctx->pfh_rb_mem);
-  if (ctx->spin_rb_mem) (void)hipHostFree(ctx->spin_rb_mem);
-  if (ctx->rift_rb_mem) (void)hipHostFree(ctx->rift_rb_mem);
-  if (ctx->sc_rb_mem) (void)hipHostFree(ctx->sc_rb_mem);
-  if (ctx->moments_rb_mem) (void)hipHostFree(ctx->moments_rb_mem);
+  if (ctx->reports.host) (void)hipHostFree(ctx->reports.host);
   delete ctx;
 }
 
@@ -192,12 +204,7 @@ pfx_status pfx_ctx_trim(pfx_ctx* ctx) {
   pfx::normals_finish_dev(ctx);
   ctx->lists_gate = nullptr;  // a borrowed event the next call must not wait on
   PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::fpfh_resolve(ctx);
-  pfx::pfh_resolve(ctx);
-  pfx::spin_resolve(ctx);
-  pfx::rift_resolve(ctx);
-  pfx::sc_resolve(ctx);
-  pfx::moments_resolve(ctx);
+  pfx::reports_resolve(ctx);
   pfx::narf_release(ctx);
   pfx::normals_release(ctx);
   pfx::keypoints_release(ctx);
@@ -217,12 +224,7 @@ pfx_status pfx_ctx_synchronize(pfx_ctx* ctx) {
   PFX_API_BEGIN
   check_ctx(ctx);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::fpfh_resolve(ctx);  // deferred statistics / capacity errors of the stream-ordered calls
-  pfx::pfh_resolve(ctx);
-  pfx::spin_resolve(ctx);
-  pfx::rift_resolve(ctx);
-  pfx::sc_resolve(ctx);
-  pfx::moments_resolve(ctx);
+  pfx::reports_resolve(ctx);  // deferred statistics / capacity errors of the stream-ordered calls
   PFX_API_END(ctx)
 }
 
@@ -264,15 +266,9 @@ pfx_status pfx_ctx_kernel_time(pfx_ctx* ctx, const char* name, double* total_ms,
 pfx_status pfx_ctx_last_stats(pfx_ctx* ctx, const char* what, int64_t* value) {
   PFX_API_BEGIN
   if (!ctx || !what || !value) throw Error(PFX_ERR_INVALID, "null argument");
-  if (ctx->fpfh_pending || ctx->pfh_pending || ctx->spin_pending || ctx->igrad_pending || ctx->rift_pending ||
-      ctx->sc_pending || ctx->lrf_pending || ctx->moments_pending || ctx->pcurv_pending) {
+  if (ctx->reports.any()) {
     PFX_HIP(hipStreamSynchronize(ctx->stream));
-    pfx::fpfh_resolve(ctx);
-    pfx::pfh_resolve(ctx);
-    pfx::spin_resolve(ctx);
-    pfx::rift_resolve(ctx);
-    pfx::sc_resolve(ctx);
-    pfx::moments_resolve(ctx);
+    pfx::reports_resolve(ctx);
   }
   auto it = ctx->stats.find(what);
   if (it == ctx->stats.end()) throw Error(PFX_ERR_INVALID, std::string("unknown stat ") + what);
@@ -522,23 +518,13 @@ pfx_status pfx_fpfh(pfx_ctx* ctx, const float* sx, const float* sy, const float*
   if (n_surface < 0 || nq < 0 || (nq && !out)) throw Error(PFX_ERR_INVALID, "fpfh: invalid arguments");
   if (same_as_surface && nq != n_surface)
     throw Error(PFX_ERR_INVALID, "fpfh: same_as_surface requires nq == n_surface");
-  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
-  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
-  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
-  float* dnx = stage_in(ctx, "in_nx", snx, n_surface);
-  float* dny = stage_in(ctx, "in_ny", sny, n_surface);
-  float* dnz = stage_in(ctx, "in_nz", snz, n_surface);
-  float *dqx = dsx, *dqy = dsy, *dqz = dsz;
-  if (!same_as_surface) {
-    dqx = stage_in(ctx, "in_qx", qx, nq);
-    dqy = stage_in(ctx, "in_qy", qy, nq);
-    dqz = stage_in(ctx, "in_qz", qz, nq);
-  }
+  const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), n = stage3(ctx, "in_n", snx, sny, snz, n_surface);
+  const Dev3 q = same_as_surface ? s : stage3(ctx, "in_q", qx, qy, qz, nq);
   float* dout = ctx->buf("out_fpfh").as<float>(nq * 33 + 1);
-  pfx::fpfh_dev(ctx, dsx, dsy, dsz, dnx, dny, dnz, n_surface, dqx, dqy, dqz, nq, same_as_surface, radius, dout);
-  if (nq) PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * 33, hipMemcpyDeviceToHost, ctx->stream));
+  pfx::fpfh_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, n_surface, q.x, q.y, q.z, nq, same_as_surface, radius, dout);
+  rows_out(ctx, out, dout, nq, 33);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::fpfh_resolve(ctx);  // the host API reports at once
+  pfx::reports_resolve(ctx, pfx::kRepFpfh, pfx::kRepFpfh);  // the host API reports at once
   PFX_API_END(ctx)
 }
 
@@ -584,22 +570,13 @@ pfx_status pfx_shot(pfx_ctx* ctx, const float* sx, const float* sy, const float*
   PFX_API_BEGIN
   check_ctx(ctx);
   if (n_surface < 0 || nq < 0 || (nq && (!desc || !rf))) throw Error(PFX_ERR_INVALID, "shot: invalid arguments");
-  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
-  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
-  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
-  float* dnx = stage_in(ctx, "in_nx", snx, n_surface);
-  float* dny = stage_in(ctx, "in_ny", sny, n_surface);
-  float* dnz = stage_in(ctx, "in_nz", snz, n_surface);
-  float* dqx = stage_in(ctx, "in_qx", qx, nq);
-  float* dqy = stage_in(ctx, "in_qy", qy, nq);
-  float* dqz = stage_in(ctx, "in_qz", qz, nq);
+  const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), n = stage3(ctx, "in_n", snx, sny, snz, n_surface);
+  const Dev3 q = stage3(ctx, "in_q", qx, qy, qz, nq);
   float* ddesc = ctx->buf("out_shot").as<float>(nq * 352 + 1);
   float* drf = ctx->buf("out_rf").as<float>(nq * 9 + 1);
-  pfx::shot_dev(ctx, dsx, dsy, dsz, dnx, dny, dnz, n_surface, dqx, dqy, dqz, nq, radius, ddesc, drf);
-  if (nq) {
-    PFX_HIP(hipMemcpyAsync(desc, ddesc, sizeof(float) * nq * 352, hipMemcpyDeviceToHost, ctx->stream));
-    PFX_HIP(hipMemcpyAsync(rf, drf, sizeof(float) * nq * 9, hipMemcpyDeviceToHost, ctx->stream));
-  }
+  pfx::shot_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, n_surface, q.x, q.y, q.z, nq, radius, ddesc, drf);
+  rows_out(ctx, desc, ddesc, nq, 352);
+  rows_out(ctx, rf, drf, nq, 9);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   PFX_API_END(ctx)
 }
@@ -629,26 +606,17 @@ pfx_status pfx_shot_color(pfx_ctx* ctx, const float* sx, const float* sy, const 
   if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!desc || !rf || !qx || !qy || !qz || !qrgb)) ||
       (n_surface && (!sx || !sy || !sz || !snx || !sny || !snz || !srgb)))
     throw Error(PFX_ERR_INVALID, "shot_color: invalid arguments");
-  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
-  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
-  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
-  float* dnx = stage_in(ctx, "in_nx", snx, n_surface);
-  float* dny = stage_in(ctx, "in_ny", sny, n_surface);
-  float* dnz = stage_in(ctx, "in_nz", snz, n_surface);
+  const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), n = stage3(ctx, "in_n", snx, sny, snz, n_surface);
   // (the packed colours are staged as the 32-bit words they are)
   float* drgb = stage_in(ctx, "in_rgb", reinterpret_cast<const float*>(srgb), n_surface);
-  float* dqx = stage_in(ctx, "in_qx", qx, nq);
-  float* dqy = stage_in(ctx, "in_qy", qy, nq);
-  float* dqz = stage_in(ctx, "in_qz", qz, nq);
+  const Dev3 q = stage3(ctx, "in_q", qx, qy, qz, nq);
   float* dqrgb = stage_in(ctx, "in_qrgb", reinterpret_cast<const float*>(qrgb), nq);
   float* ddesc = ctx->buf("out_shot_color").as<float>(nq * 1344 + 1);
   float* drf = ctx->buf("out_rf").as<float>(nq * 9 + 1);
-  pfx::shot_color_dev(ctx, dsx, dsy, dsz, dnx, dny, dnz, reinterpret_cast<const uint32_t*>(drgb), n_surface, dqx, dqy,
-                      dqz, reinterpret_cast<const uint32_t*>(dqrgb), nq, radius, ddesc, drf);
-  if (nq) {
-    PFX_HIP(hipMemcpyAsync(desc, ddesc, sizeof(float) * nq * 1344, hipMemcpyDeviceToHost, ctx->stream));
-    PFX_HIP(hipMemcpyAsync(rf, drf, sizeof(float) * nq * 9, hipMemcpyDeviceToHost, ctx->stream));
-  }
+  pfx::shot_color_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, reinterpret_cast<const uint32_t*>(drgb), n_surface, q.x, q.y,
+                      q.z, reinterpret_cast<const uint32_t*>(dqrgb), nq, radius, ddesc, drf);
+  rows_out(ctx, desc, ddesc, nq, 1344);
+  rows_out(ctx, rf, drf, nq, 9);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   PFX_API_END(ctx)
 }
@@ -673,20 +641,13 @@ pfx_status pfx_pfh(pfx_ctx* ctx, const float* sx, const float* sy, const float* 
   if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!out || !qx || !qy || !qz)) ||
       (n_surface && (!sx || !sy || !sz || !snx || !sny || !snz)))
     throw Error(PFX_ERR_INVALID, "pfh: invalid arguments");
-  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
-  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
-  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
-  float* dnx = stage_in(ctx, "in_nx", snx, n_surface);
-  float* dny = stage_in(ctx, "in_ny", sny, n_surface);
-  float* dnz = stage_in(ctx, "in_nz", snz, n_surface);
-  float* dqx = stage_in(ctx, "in_qx", qx, nq);
-  float* dqy = stage_in(ctx, "in_qy", qy, nq);
-  float* dqz = stage_in(ctx, "in_qz", qz, nq);
+  const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), n = stage3(ctx, "in_n", snx, sny, snz, n_surface);
+  const Dev3 q = stage3(ctx, "in_q", qx, qy, qz, nq);
   float* dout = ctx->buf("out_pfh").as<float>(nq * 125 + 1);
-  pfx::pfh_dev(ctx, dsx, dsy, dsz, dnx, dny, dnz, n_surface, dqx, dqy, dqz, nq, radius, dout);
-  if (nq) PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * 125, hipMemcpyDeviceToHost, ctx->stream));
+  pfx::pfh_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, n_surface, q.x, q.y, q.z, nq, radius, dout);
+  rows_out(ctx, out, dout, nq, 125);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::pfh_resolve(ctx);  // the host API reports at once
+  pfx::reports_resolve(ctx, pfx::kRepPfh, pfx::kRepPfh);  // the host API reports at once
   PFX_API_END(ctx)
 }
 
@@ -741,30 +702,19 @@ pfx_status pfx_spin_image(pfx_ctx* ctx, const float* sx, const float* sy, const 
   spin_check(sx, sy, sz, snx, sny, snz, n_surface, qx, qy, qz, qnx, qny, qnz, nq, radius, params, out);
   const bool normals = params->support_angle_cos > 0.0 && n_surface;
   const int64_t S = (int64_t)(params->image_width + 1) * (2 * params->image_width + 1);
-  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
-  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
-  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
-  float* dnx = normals ? stage_in(ctx, "in_nx", snx, n_surface) : nullptr;
-  float* dny = normals ? stage_in(ctx, "in_ny", sny, n_surface) : nullptr;
-  float* dnz = normals ? stage_in(ctx, "in_nz", snz, n_surface) : nullptr;
-  float* dqx = stage_in(ctx, "in_qx", qx, nq);
-  float* dqy = stage_in(ctx, "in_qy", qy, nq);
-  float* dqz = stage_in(ctx, "in_qz", qz, nq);
-  float* dax = stage_in(ctx, "in_qnx", qnx, nq);
-  float* day = stage_in(ctx, "in_qny", qny, nq);
-  float* daz = stage_in(ctx, "in_qnz", qnz, nq);
+  const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface);
+  const Dev3 n = normals ? stage3(ctx, "in_n", snx, sny, snz, n_surface) : Dev3{nullptr, nullptr, nullptr};
+  const Dev3 q = stage3(ctx, "in_q", qx, qy, qz, nq), a = stage3(ctx, "in_qn", qnx, qny, qnz, nq);
   float* dout = ctx->buf("out_spin").as<float>(nq * S + 1);
   double* draw = raw ? ctx->buf("out_spin_raw").as<double>(nq * S + 1) : nullptr;
   double* dsums = sums ? ctx->buf("out_spin_sums").as<double>(nq + 1) : nullptr;
-  pfx::spin_dev(ctx, dsx, dsy, dsz, dnx, dny, dnz, n_surface, dqx, dqy, dqz, dax, day, daz, nq, radius, *params, dout,
+  pfx::spin_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, n_surface, q.x, q.y, q.z, a.x, a.y, a.z, nq, radius, *params, dout,
                 draw, dsums);
-  if (nq) {
-    PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * S, hipMemcpyDeviceToHost, ctx->stream));
-    if (raw) PFX_HIP(hipMemcpyAsync(raw, draw, sizeof(double) * nq * S, hipMemcpyDeviceToHost, ctx->stream));
-    if (sums) PFX_HIP(hipMemcpyAsync(sums, dsums, sizeof(double) * nq, hipMemcpyDeviceToHost, ctx->stream));
-  }
+  rows_out(ctx, out, dout, nq, S);
+  rows_out(ctx, raw, draw, nq, S);
+  rows_out(ctx, sums, dsums, nq, 1);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::spin_resolve(ctx);  // the host API reports at once
+  pfx::reports_resolve(ctx, pfx::kRepSpin, pfx::kRepSpin);  // the host API reports at once
   PFX_API_END(ctx)
 }
 
@@ -799,22 +749,16 @@ pfx_status pfx_intensity_gradient(pfx_ctx* ctx, const float* sx, const float* sy
   PFX_API_BEGIN
   check_ctx(ctx);
   igrad_check(sx, sy, sz, si, n_surface, qx, qy, qz, qnx, qny, qnz, nq, same_as_surface, false, radius, out);
-  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
-  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
-  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
+  const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface);
   float* dsi = stage_in(ctx, "in_i", si, n_surface);
   // (the whole-cloud path reads the surface's own arrays as its queries)
-  float* dqx = same_as_surface ? dsx : stage_in(ctx, "in_qx", qx, nq);
-  float* dqy = same_as_surface ? dsy : stage_in(ctx, "in_qy", qy, nq);
-  float* dqz = same_as_surface ? dsz : stage_in(ctx, "in_qz", qz, nq);
-  float* dnx = stage_in(ctx, "in_qnx", qnx, nq);
-  float* dny = stage_in(ctx, "in_qny", qny, nq);
-  float* dnz = stage_in(ctx, "in_qnz", qnz, nq);
+  const Dev3 q = same_as_surface ? s : stage3(ctx, "in_q", qx, qy, qz, nq);
+  const Dev3 n = stage3(ctx, "in_qn", qnx, qny, qnz, nq);
   float* dout = ctx->buf("out_igrad").as<float>(nq * 3 + 1);
-  pfx::igrad_dev(ctx, dsx, dsy, dsz, dsi, n_surface, dqx, dqy, dqz, dnx, dny, dnz, nq, same_as_surface, radius, dout);
-  if (nq) PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * 3, hipMemcpyDeviceToHost, ctx->stream));
+  pfx::igrad_dev(ctx, s.x, s.y, s.z, dsi, n_surface, q.x, q.y, q.z, n.x, n.y, n.z, nq, same_as_surface, radius, dout);
+  rows_out(ctx, out, dout, nq, 3);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::rift_resolve(ctx);  // the host API reports at once
+  pfx::reports_resolve(ctx, pfx::kRepIgrad, pfx::kRepRift);  // the host API reports at once
   PFX_API_END(ctx)
 }
 
@@ -849,21 +793,15 @@ pfx_status pfx_rift(pfx_ctx* ctx, const float* sx, const float* sy, const float*
   check_ctx(ctx);
   rift_check(sx, sy, sz, sgx, sgy, sgz, n_surface, cx, cy, cz, nq, radius, nr_distance_bins, nr_gradient_bins, out);
   const int64_t S = (int64_t)nr_distance_bins * nr_gradient_bins;
-  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
-  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
-  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
-  float* dgx = stage_in(ctx, "in_nx", sgx, n_surface);
-  float* dgy = stage_in(ctx, "in_ny", sgy, n_surface);
-  float* dgz = stage_in(ctx, "in_nz", sgz, n_surface);
-  float* dcx = stage_in(ctx, "in_qx", cx, nq);
-  float* dcy = stage_in(ctx, "in_qy", cy, nq);
-  float* dcz = stage_in(ctx, "in_qz", cz, nq);
+  // (the gradients ride in the normals' buffers)
+  const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), g = stage3(ctx, "in_n", sgx, sgy, sgz, n_surface);
+  const Dev3 c = stage3(ctx, "in_q", cx, cy, cz, nq);
   float* dout = ctx->buf("out_rift").as<float>(nq * S + 1);
-  pfx::rift_dev(ctx, dsx, dsy, dsz, dgx, dgy, dgz, n_surface, dcx, dcy, dcz, nq, radius, nr_distance_bins,
+  pfx::rift_dev(ctx, s.x, s.y, s.z, g.x, g.y, g.z, n_surface, c.x, c.y, c.z, nq, radius, nr_distance_bins,
                 nr_gradient_bins, dout);
-  if (nq) PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * S, hipMemcpyDeviceToHost, ctx->stream));
+  rows_out(ctx, out, dout, nq, S);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::rift_resolve(ctx);  // the host API reports at once
+  pfx::reports_resolve(ctx, pfx::kRepIgrad, pfx::kRepRift);  // the host API reports at once
   PFX_API_END(ctx)
 }
 
@@ -892,17 +830,12 @@ pfx_status pfx_moment_invariants(pfx_ctx* ctx, const float* sx, const float* sy,
   check_ctx(ctx);
   moments_check(sx, sy, sz, n_surface, qx, qy, qz, nq, radius, out);
   if (nq) {
-    float* dsx = stage_in(ctx, "in_x", sx, n_surface);
-    float* dsy = stage_in(ctx, "in_y", sy, n_surface);
-    float* dsz = stage_in(ctx, "in_z", sz, n_surface);
-    float* dqx = stage_in(ctx, "in_qx", qx, nq);
-    float* dqy = stage_in(ctx, "in_qy", qy, nq);
-    float* dqz = stage_in(ctx, "in_qz", qz, nq);
+    const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), q = stage3(ctx, "in_q", qx, qy, qz, nq);
     float* dout = ctx->buf("out_moments").as<float>(nq * 3 + 1);
-    pfx::moments_dev(ctx, dsx, dsy, dsz, n_surface, dqx, dqy, dqz, nq, radius, dout);
-    PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * 3, hipMemcpyDeviceToHost, ctx->stream));
+    pfx::moments_dev(ctx, s.x, s.y, s.z, n_surface, q.x, q.y, q.z, nq, radius, dout);
+    rows_out(ctx, out, dout, nq, 3);
     PFX_HIP(hipStreamSynchronize(ctx->stream));
-    pfx::moments_resolve(ctx);  // the host API reports at once
+    pfx::reports_resolve(ctx, pfx::kRepMoments, pfx::kRepPcurv);  // the host API reports at once
   }
   PFX_API_END(ctx)
 }
@@ -938,23 +871,13 @@ pfx_status pfx_principal_curvatures(pfx_ctx* ctx, const float* sx, const float* 
   check_ctx(ctx);
   pcurv_check(sx, sy, sz, snx, sny, snz, n_surface, qx, qy, qz, qnx, qny, qnz, nq, radius, out);
   if (nq) {
-    float* dsx = stage_in(ctx, "in_x", sx, n_surface);
-    float* dsy = stage_in(ctx, "in_y", sy, n_surface);
-    float* dsz = stage_in(ctx, "in_z", sz, n_surface);
-    float* dnx = stage_in(ctx, "in_nx", snx, n_surface);
-    float* dny = stage_in(ctx, "in_ny", sny, n_surface);
-    float* dnz = stage_in(ctx, "in_nz", snz, n_surface);
-    float* dqx = stage_in(ctx, "in_qx", qx, nq);
-    float* dqy = stage_in(ctx, "in_qy", qy, nq);
-    float* dqz = stage_in(ctx, "in_qz", qz, nq);
-    float* dax = stage_in(ctx, "in_qnx", qnx, nq);
-    float* day = stage_in(ctx, "in_qny", qny, nq);
-    float* daz = stage_in(ctx, "in_qnz", qnz, nq);
+    const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), n = stage3(ctx, "in_n", snx, sny, snz, n_surface);
+    const Dev3 q = stage3(ctx, "in_q", qx, qy, qz, nq), a = stage3(ctx, "in_qn", qnx, qny, qnz, nq);
     float* dout = ctx->buf("out_pcurv").as<float>(nq * 5 + 1);
-    pfx::pcurv_dev(ctx, dsx, dsy, dsz, dnx, dny, dnz, n_surface, dqx, dqy, dqz, dax, day, daz, nq, radius, dout);
-    PFX_HIP(hipMemcpyAsync(out, dout, sizeof(float) * nq * 5, hipMemcpyDeviceToHost, ctx->stream));
+    pfx::pcurv_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, n_surface, q.x, q.y, q.z, a.x, a.y, a.z, nq, radius, dout);
+    rows_out(ctx, out, dout, nq, 5);
     PFX_HIP(hipStreamSynchronize(ctx->stream));
-    pfx::moments_resolve(ctx);  // the host API reports at once
+    pfx::reports_resolve(ctx, pfx::kRepMoments, pfx::kRepPcurv);  // the host API reports at once
   }
   PFX_API_END(ctx)
 }
@@ -995,26 +918,17 @@ pfx_status pfx_shape_context(pfx_ctx* ctx, const float* sx, const float* sy, con
   check_ctx(ctx);
   sc_check("shape_context", sx, sy, sz, snx && sny && snz, n_surface, qx, qy, qz, true, nq, radius, min_radius,
            point_density_radius, desc, rf);
-  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
-  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
-  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
-  float* dnx = stage_in(ctx, "in_nx", snx, n_surface);
-  float* dny = stage_in(ctx, "in_ny", sny, n_surface);
-  float* dnz = stage_in(ctx, "in_nz", snz, n_surface);
-  float* dqx = stage_in(ctx, "in_qx", qx, nq);
-  float* dqy = stage_in(ctx, "in_qy", qy, nq);
-  float* dqz = stage_in(ctx, "in_qz", qz, nq);
+  const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), n = stage3(ctx, "in_n", snx, sny, snz, n_surface);
+  const Dev3 q = stage3(ctx, "in_q", qx, qy, qz, nq);
   float* drnd = rnd ? stage_in(ctx, "in_sc_rnd", rnd, 3 * nq) : nullptr;
   float* ddesc = ctx->buf("out_sc").as<float>(nq * 1980 + 1);
   float* drf = ctx->buf("out_sc_rf").as<float>(nq * 9 + 1);
-  pfx::sc_dev(ctx, dsx, dsy, dsz, dnx, dny, dnz, n_surface, dqx, dqy, dqz, nullptr, nq, radius, min_radius,
+  pfx::sc_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, n_surface, q.x, q.y, q.z, nullptr, nq, radius, min_radius,
               point_density_radius, drnd, ddesc, drf);
-  if (nq) {
-    PFX_HIP(hipMemcpyAsync(desc, ddesc, sizeof(float) * nq * 1980, hipMemcpyDeviceToHost, ctx->stream));
-    PFX_HIP(hipMemcpyAsync(rf, drf, sizeof(float) * nq * 9, hipMemcpyDeviceToHost, ctx->stream));
-  }
+  rows_out(ctx, desc, ddesc, nq, 1980);
+  rows_out(ctx, rf, drf, nq, 9);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::sc_resolve(ctx);  // the host API reports at once
+  pfx::reports_resolve(ctx, pfx::kRepSc, pfx::kRepLrf);  // the host API reports at once
   PFX_API_END(ctx)
 }
 
@@ -1038,23 +952,18 @@ pfx_status pfx_usc(pfx_ctx* ctx, const float* sx, const float* sy, const float* 
   check_ctx(ctx);
   sc_check("usc", sx, sy, sz, true, n_surface, qx, qy, qz, frames != nullptr, nq, radius, min_radius,
            point_density_radius, desc, rf);
-  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
-  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
-  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
-  float* dqx = stage_in(ctx, "in_qx", qx, nq);
-  float* dqy = stage_in(ctx, "in_qy", qy, nq);
-  float* dqz = stage_in(ctx, "in_qz", qz, nq);
+  const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), q = stage3(ctx, "in_q", qx, qy, qz, nq);
   float* dfr = stage_in(ctx, "in_sc_frames", frames, 9 * nq);
   float* ddesc = ctx->buf("out_sc").as<float>(nq * 1980 + 1);
   float* drf = ctx->buf("out_sc_rf").as<float>(nq * 9 + 1);
-  if (nq) {
-    pfx::sc_dev(ctx, dsx, dsy, dsz, nullptr, nullptr, nullptr, n_surface, dqx, dqy, dqz, dfr, nq, radius, min_radius,
+  // (sc_dev tells the USC by its frames, and without queries they may be null)
+  if (nq)
+    pfx::sc_dev(ctx, s.x, s.y, s.z, nullptr, nullptr, nullptr, n_surface, q.x, q.y, q.z, dfr, nq, radius, min_radius,
                 point_density_radius, nullptr, ddesc, drf);
-    PFX_HIP(hipMemcpyAsync(desc, ddesc, sizeof(float) * nq * 1980, hipMemcpyDeviceToHost, ctx->stream));
-    PFX_HIP(hipMemcpyAsync(rf, drf, sizeof(float) * nq * 9, hipMemcpyDeviceToHost, ctx->stream));
-  }
+  rows_out(ctx, desc, ddesc, nq, 1980);
+  rows_out(ctx, rf, drf, nq, 9);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::sc_resolve(ctx);  // the host API reports at once
+  pfx::reports_resolve(ctx, pfx::kRepSc, pfx::kRepLrf);  // the host API reports at once
   PFX_API_END(ctx)
 }
 
@@ -1080,17 +989,12 @@ pfx_status pfx_shot_lrf(pfx_ctx* ctx, const float* sx, const float* sy, const fl
   PFX_API_BEGIN
   check_ctx(ctx);
   lrf_check(sx, sy, sz, n_surface, qx, qy, qz, nq, radius, rf);
-  float* dsx = stage_in(ctx, "in_x", sx, n_surface);
-  float* dsy = stage_in(ctx, "in_y", sy, n_surface);
-  float* dsz = stage_in(ctx, "in_z", sz, n_surface);
-  float* dqx = stage_in(ctx, "in_qx", qx, nq);
-  float* dqy = stage_in(ctx, "in_qy", qy, nq);
-  float* dqz = stage_in(ctx, "in_qz", qz, nq);
+  const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), q = stage3(ctx, "in_q", qx, qy, qz, nq);
   float* drf = ctx->buf("out_sc_rf").as<float>(nq * 9 + 1);
-  pfx::shot_lrf_dev(ctx, dsx, dsy, dsz, n_surface, dqx, dqy, dqz, nq, radius, drf);
-  if (nq) PFX_HIP(hipMemcpyAsync(rf, drf, sizeof(float) * nq * 9, hipMemcpyDeviceToHost, ctx->stream));
+  pfx::shot_lrf_dev(ctx, s.x, s.y, s.z, n_surface, q.x, q.y, q.z, nq, radius, drf);
+  rows_out(ctx, rf, drf, nq, 9);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::sc_resolve(ctx);  // the host API reports at once
+  pfx::reports_resolve(ctx, pfx::kRepSc, pfx::kRepLrf);  // the host API reports at once
   PFX_API_END(ctx)
 }
 

@@ -19,6 +19,16 @@ namespace pfx {
 
 struct f3 { float x, y, z; };
 
+// a NaN as the restatements write it (0x7fc00000), whatever its sign and payload
+__device__ __forceinline__ float canon_nan(float v) { return v != v ? __uint_as_float(0x7fc00000u) : v; }
+
+// p[0..n) = v, blocks of 256 threads
+template <class T>
+__global__ void k_fill(T* __restrict__ p, int64_t n, T v) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
 __device__ __forceinline__ f3 mk3(float x, float y, float z) { f3 r; r.x = x; r.y = y; r.z = z; return r; }
 __device__ __forceinline__ f3 sub3(f3 a, f3 b) { return mk3(a.x - b.x, a.y - b.y, a.z - b.z); }
 __device__ __forceinline__ f3 add3(f3 a, f3 b) { return mk3(a.x + b.x, a.y + b.y, a.z + b.z); }

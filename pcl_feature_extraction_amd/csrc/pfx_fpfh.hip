@@ -1039,6 +1039,24 @@ bool fpfh_validate_grid(pfx_ctx* ctx) {
   return true;
 }
 
+// the surface grid prepared ahead (pfx_fpfh_prepare_dev: coordinates only), else built here
+GridView feature_grid(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, double r) {
+  const bool grid_ready = ctx->prep_x == sx && ctx->prep_n == ns && ctx->prep_r == r;
+  if (grid_ready) fpfh_validate_grid(ctx);  // (a speculative prepared grid: exact after this)
+  ctx->prep_x = nullptr;  // one-shot
+  ctx->prep_n = -1;
+  ctx->prep_qx = nullptr;
+  ctx->prep_nq = -1;
+  if (!grid_ready) build_grid(ctx, ctx->grid_b, sx, sy, sz, ns, r);
+  return view(ctx->grid_b);
+}
+
+// grid_b prepared for (sx, ns, r), now unless it already is, and exact; the preparation stands
+static void prepared_grid(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, double r) {
+  if (!(ctx->prep_x == sx && ctx->prep_n == ns && ctx->prep_r == r)) fpfh_prepare_dev(ctx, sx, sy, sz, ns, r);
+  fpfh_validate_grid(ctx);
+}
+
 // S of the next fpfh_dev (input != surface) marked and compacted ahead of time: it needs only the
 // coordinates and the queries, so it can run while the normals are still being computed.
 void fpfh_prepare_queries_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns,
@@ -1047,8 +1065,7 @@ void fpfh_prepare_queries_dev(pfx_ctx* ctx, const float* sx, const float* sy, co
   ctx->prep_qx = nullptr;
   ctx->prep_nq = -1;
   if (ns == 0 || nq == 0) return;
-  if (!(ctx->prep_x == sx && ctx->prep_n == ns && ctx->prep_r == r)) fpfh_prepare_dev(ctx, sx, sy, sz, ns, r);
-  fpfh_validate_grid(ctx);
+  prepared_grid(ctx, sx, sy, sz, ns, r);
   hipStream_t st = ctx->stream;
   const Grid& G = ctx->grid_b;
   uint8_t* flags = ctx->buf("fpfh_flags").as<uint8_t>(ns);
@@ -1086,8 +1103,7 @@ void fpfh_support_mask_dev(pfx_ctx* ctx, const float* sx, const float* sy, const
   hipStream_t st = ctx->stream;
   PFX_HIP(hipMemsetAsync(mask, 0, ns, st));
   if (nq == 0) return;
-  if (!(ctx->prep_x == sx && ctx->prep_n == ns && ctx->prep_r == r)) fpfh_prepare_dev(ctx, sx, sy, sz, ns, r);
-  fpfh_validate_grid(ctx);
+  prepared_grid(ctx, sx, sy, sz, ns, r);
   TimeScope ts(ctx, "fpfh_support");
   const Grid& G = ctx->grid_b;
   const GridView g = view(G);
@@ -1116,8 +1132,7 @@ void fpfh_support_ball_dev(pfx_ctx* ctx, const float* sx, const float* sy, const
   hipStream_t st = ctx->stream;
   PFX_HIP(hipMemsetAsync(mask, 0, ns, st));
   if (nq == 0) return;
-  if (!(ctx->prep_x == sx && ctx->prep_n == ns && ctx->prep_r == r)) fpfh_prepare_dev(ctx, sx, sy, sz, ns, r);
-  fpfh_validate_grid(ctx);
+  prepared_grid(ctx, sx, sy, sz, ns, r);
   TimeScope ts(ctx, "fpfh_support");
   // (2r)^2 with a relative margin far above the float rounding of the squared distance
   const float rr4 = (float)(4.0 * r * r * (1.0 + 1e-5));
@@ -1140,6 +1155,8 @@ void fpfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, c
     PFX_HIP(hipStreamSynchronize(st));
     return;
   }
+  // (not feature_grid: whether a prepared grid was rebuilt decides what else of the preparation
+  // stands, so it is validated after the build, and prep_qx is read before the preparation is spent)
   const bool grid_ready = ctx->prep_x == sx && ctx->prep_n == ns && ctx->prep_r == r;
   if (!grid_ready) build_grid(ctx, ctx->grid_b, sx, sy, sz, ns, r);
   const bool rebuilt = grid_ready && fpfh_validate_grid(ctx);
@@ -1166,15 +1183,13 @@ void fpfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, c
   void* tmp = ctx->buf("fpfh_tmp").get(tmp_bytes + 16);
   const unsigned nb = (unsigned)ceil_div(ns, 256);
   // [0] k over capacity, [1] max k, [2] inexact sums, [3] deferred pairs, [4..7] pairs,
-  // [8] queries over the LDS capacity (weighted by the global-scratch pass)
-  DevBuf& eb = ctx->buf("fpfh_err");
-  const bool fresh = !eb.ptr;
-  int* err = eb.as<int>(10);
-  if (fresh) PFX_HIP(hipMemsetAsync(err, 0, 10 * sizeof(int), st));  // the sticky word starts clear
+  // [8] queries over the LDS capacity (weighted by the global-scratch pass); in pinned memory
+  // also [10..11] the S count (i64) and [12] slow_cap
+  int* err = report_words(ctx, kRepFpfh, /*clear_per_call=*/false);
   {
     TimeScope ts(ctx, "fpfh_mark");
     // (also zeroes the per-call statistics words err[1..9]: err[0] (neighbourhood beyond
-    // capacity) is sticky until the check after the next synchronisation, fpfh_resolve)
+    // capacity) is sticky until the check after the next synchronisation, fpfh_report)
     // few queries on a large surface: only the cells FPFH can read (threshold not swept: a query's
     // 125 cells hold up to ~2^14 points of the 1M-point room, and the copy must stay below ns)
     if (!same && nq * 4096 <= ns)
@@ -1276,38 +1291,31 @@ void fpfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, c
   }
   // statistics and the sticky error word land in pinned memory in stream order; no host
   // synchronisation here (the step's critical path ends with this call)
-  FpfhReadback* rb = ctx->fpfh_rb();
-  PFX_HIP(hipMemcpyAsync(rb->h, err, sizeof(rb->h), hipMemcpyDeviceToHost, st));
-  PFX_HIP(hipMemcpyAsync(&rb->count, d_sel, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  rb->slow_cap = slow_cap;
-  ctx->fpfh_pending = true;
+  report_post(ctx, kRepFpfh, err, 10);
+  int* h = report_host(ctx, kRepFpfh);
+  PFX_HIP(hipMemcpyAsync(h + 10, d_sel, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  h[12] = (int)slow_cap;
 }
 
-// After a synchronisation of ctx's stream: the last fpfh_dev's statistics, and its capacity check
-// (PFX_ERR_CAPACITY, reported here for the stream-ordered API; the host API calls this at once).
-void fpfh_resolve(pfx_ctx* ctx) {
-  if (!ctx->fpfh_pending) return;
-  ctx->fpfh_pending = false;
-  const FpfhReadback* rb = ctx->fpfh_rb();
-  const int* h = rb->h;
-  const unsigned n_slow = (unsigned)h[3];
-  ctx->stats["fpfh_spfh_points"] = rb->count;
+// The last fpfh_dev's statistics, and its capacity check (PFX_ERR_CAPACITY).
+void fpfh_report(pfx_ctx* ctx, const int* h) {
+  const unsigned n_slow = (unsigned)h[3], slow_cap = (unsigned)h[12];
+  int64_t count;
+  std::memcpy(&count, h + 10, sizeof(count));
+  ctx->stats["fpfh_spfh_points"] = count;
   unsigned long long pr;
   std::memcpy(&pr, h + 4, sizeof(pr));
   ctx->stats["fpfh_spfh_pairs"] = (int64_t)pr;
   std::memcpy(&pr, h + 6, sizeof(pr));
   ctx->stats["fpfh_spfh_exact_pairs"] = (int64_t)pr;
   ctx->stats["fpfh_spfh_deferred"] = n_slow;
-  ctx->stats["fpfh_spfh_inline_exact"] = n_slow > rb->slow_cap ? n_slow - rb->slow_cap : 0;
+  ctx->stats["fpfh_spfh_inline_exact"] = n_slow > slow_cap ? n_slow - slow_cap : 0;
   ctx->stats["fpfh_weight_kmax"] = h[1];
   ctx->stats["fpfh_weight_sequential"] = h[2];
   ctx->stats["fpfh_weight_global"] = h[8];
-  if (h[0] > 0) {
-    int* err = ctx->buf("fpfh_err").as<int>(10);
-    PFX_HIP(hipMemsetAsync(err, 0, sizeof(int), ctx->stream));  // reported once
+  if (h[0] > 0)
     throw Error(PFX_ERR_CAPACITY, "fpfh: a query has " + std::to_string(h[0]) + " neighbours (> " +
                                       std::to_string(kCapWGlobal) + " supported)");
-  }
 }
 
 }  // namespace pfx

@@ -126,10 +126,22 @@ struct GridView {
   int32_t nx, ny, nz;
 };
 
-struct FpfhReadback {  // pfx_fpfh.hip
-  int h[10];
-  int64_t count;
-  unsigned slow_cap;
+// Deferred reports (pfx_report.hip, DESIGN.md "The descriptors' common frame"): a stream-ordered
+// call leaves its statistics and error words on the device, copies them to its slot of one pinned
+// block in stream order, and they are read after the next synchronisation.  One slot per kind of
+// call, resolved in this order.
+enum ReportSlot {
+  kRepFpfh, kRepPfh, kRepSpin, kRepIgrad, kRepRift, kRepSc, kRepLrf, kRepMoments, kRepPcurv, kReportSlots
+};
+constexpr int kReportWords = 16;  // ints of a slot, on the device and in pinned memory
+struct Reports {
+  int* host = nullptr;  // pinned, kReportSlots x kReportWords, allocated by the first call
+  bool pending[kReportSlots] = {};
+  bool any() const {
+    for (bool p : pending)
+      if (p) return true;
+    return false;
+  }
 };
 
 struct NarfState;     // pfx_narf.hip
@@ -172,29 +184,7 @@ struct pfx_ctx {
   pfx::KeypointState* kp = nullptr;      // grids + lists of the keypoint detectors
   pfx::IcpState* icp = nullptr;          // the target grids of the ICP search
   pfx::DevBuf& buf(const char* name) { return bufs[name]; }
-  // fpfh_dev's statistics / sticky error word, copied to pinned memory in stream order and read
-  // after the next synchronisation (pfx::fpfh_resolve)
-  void* fpfh_rb_mem = nullptr;
-  bool fpfh_pending = false;
-  pfx::FpfhReadback* fpfh_rb() {
-    if (!fpfh_rb_mem) PFX_HIP(hipHostMalloc(&fpfh_rb_mem, sizeof(pfx::FpfhReadback), hipHostMallocDefault));
-    return static_cast<pfx::FpfhReadback*>(fpfh_rb_mem);
-  }
-  // pfh_dev's statistics / sticky error word, the same way (pfx::pfh_resolve)
-  void* pfh_rb_mem = nullptr;
-  bool pfh_pending = false;
-  // spin_dev's statistics / error words, the same way (pfx::spin_resolve)
-  void* spin_rb_mem = nullptr;
-  bool spin_pending = false;
-  // igrad_dev's and rift_dev's, the same way (pfx::rift_resolve)
-  void* rift_rb_mem = nullptr;
-  bool igrad_pending = false, rift_pending = false;
-  // sc_dev's and shot_lrf_dev's, the same way (pfx::sc_resolve)
-  void* sc_rb_mem = nullptr;
-  bool sc_pending = false, lrf_pending = false;
-  // moments_dev's and pcurv_dev's, the same way (pfx::moments_resolve)
-  void* moments_rb_mem = nullptr;
-  bool moments_pending = false, pcurv_pending = false;
+  pfx::Reports reports;  // the stream-ordered calls' statistics and late errors (pfx::reports_resolve)
   int64_t sc_rnd_n = 0;  // floats of the default random stream held in buf("sc_rnd")
   // one side stream + fork/join events (normal estimation's long-list chains), created on first use
   hipStream_t side = nullptr;
@@ -367,8 +357,27 @@ void fpfh_support_ball_dev(pfx_ctx* ctx, const float* sx, const float* sy, const
 void radius_search_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
                        const float* qx, const float* qy, const float* qz, int64_t nq, double r,
                        int64_t* d_counts, int32_t* d_idx, float* d_d2, int64_t cap);
-// after a synchronisation of ctx->stream: the last fpfh_dev's statistics and capacity check
-void fpfh_resolve(pfx_ctx* ctx);
+// The deferred reports (pfx_report.hip).  report_words: the slot's kReportWords device words, all
+// clear when their buffer is fresh (the first call, or the first after pfx_ctx_trim), else the sticky
+// words as they stand and, unless the call's own kernels clear them, the per-call words clear.
+int* report_words(pfx_ctx* ctx, ReportSlot slot, bool clear_per_call = true);
+int* report_host(pfx_ctx* ctx, ReportSlot slot);  // the slot's pinned words
+// the first n words' copy to pinned memory in stream order (no host synchronisation); the slot is
+// pending
+void report_post(pfx_ctx* ctx, ReportSlot slot, const int* words, int n = kReportWords);
+// After a synchronisation of ctx->stream: the pending slots of [first, last] in order, each through
+// its family's finish step (*_report: the words to ctx->stats, and the Error it throws for them).  A
+// throw clears the slot's sticky device words (reported once) and leaves the later slots pending.
+void reports_resolve(pfx_ctx* ctx, ReportSlot first = kRepFpfh, ReportSlot last = kRepPcurv);
+void fpfh_report(pfx_ctx* ctx, const int* h);
+void pfh_report(pfx_ctx* ctx, const int* h);
+void spin_report(pfx_ctx* ctx, const int* h);
+void igrad_report(pfx_ctx* ctx, const int* h);
+void rift_report(pfx_ctx* ctx, const int* h);
+void sc_report(pfx_ctx* ctx, const int* h);
+void lrf_report(pfx_ctx* ctx, const int* h);
+void moments_report(pfx_ctx* ctx, const int* h);
+void pcurv_report(pfx_ctx* ctx, const int* h);
 void fpfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
               const float* sny, const float* snz, int64_t ns, const float* qx, const float* qy,
               const float* qz, int64_t nq, int same, double r, float* out,
@@ -377,6 +386,9 @@ void fpfh_prepare_dev(pfx_ctx* ctx, const float* sx, const float* sy, const floa
 // a prepared speculative grid_b checked (one pinned read, normally long complete) and rebuilt
 // exactly when a point fell outside its bounds; true when it was rebuilt
 bool fpfh_validate_grid(pfx_ctx* ctx);
+// the feature grid of a descriptor call: the one prepared ahead for (sx, ns, r), validated, else
+// built here; the preparation is spent either way
+GridView feature_grid(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, double r);
 void fpfh_prepare_queries_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns,
                               const float* qx, const float* qy, const float* qz, int64_t nq, double r);
 // pfx_shot_color.hip
@@ -388,51 +400,46 @@ void shot_color_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float*
 void shot_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
               const float* sny, const float* snz, int64_t ns, const float* qx, const float* qy,
               const float* qz, int64_t nq, double r, float* desc, float* rf);
-// PFH-125 (pfx_pfh.hip): stream-ordered, no host synchronisation; pfh_resolve as fpfh_resolve
+// The descriptor families below are stream-ordered (no host synchronisation unless noted) and
+// report through the deferred reports above.  *_cap_small: the neighbours of the first pass.
+// PFH-125 (pfx_pfh.hip)
 void pfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
              const float* sny, const float* snz, int64_t ns, const float* qx, const float* qy,
              const float* qz, int64_t nq, double r, float* out);
-void pfh_resolve(pfx_ctx* ctx);
 int pfh_cap_lds();  // neighbours a query's workgroup stages in LDS (stat "pfh_cap_lds")
-// spin images (pfx_spin.hip): stream-ordered, no host synchronisation; spin_resolve as pfh_resolve.
-// snx / sny / snz nullable unless prm.support_angle_cos > 0; raw / sums nullable
+// spin images (pfx_spin.hip): snx / sny / snz nullable unless prm.support_angle_cos > 0; raw / sums
+// nullable
 void spin_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
               const float* sny, const float* snz, int64_t ns, const float* qx, const float* qy,
               const float* qz, const float* ax, const float* ay, const float* az, int64_t nq, double r,
               const pfx_spin_params& prm, float* out, double* raw, double* sums);
-void spin_resolve(pfx_ctx* ctx);
-int spin_cap_small();  // neighbours of the first pass (stat "spin_cap_small")
-int spin_chunk();      // neighbours per accumulation chunk (stat "spin_chunk")
-// intensity gradients and RIFT (pfx_rift.hip): errors and statistics as spin images (rift_resolve
-// serves both).  igrad_dev with same != 0 (the queries are the surface) builds the normal
-// estimation's lists, with their host readback; the query path and rift_dev never wait.
+int spin_cap_small();
+int spin_chunk();  // neighbours per accumulation chunk (stat "spin_chunk")
+// intensity gradients and RIFT (pfx_rift.hip).  igrad_dev with same != 0 (the queries are the
+// surface) builds the normal estimation's lists, with their host readback.
 void igrad_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* si, int64_t ns,
                const float* qx, const float* qy, const float* qz, const float* qnx, const float* qny,
                const float* qnz, int64_t nq, int same, double r, float* out);
 void rift_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* sgx,
               const float* sgy, const float* sgz, int64_t ns, const float* cx, const float* cy, const float* cz,
               int64_t nq, double r, int D, int G, float* out);
-void rift_resolve(pfx_ctx* ctx);
-int rift_cap_small();  // neighbours of the first pass (stat "rift_cap_small")
-// 3D shape contexts, unique shape contexts and SHOT's frames alone (pfx_shape_context.hip): errors
-// and statistics as spin images (sc_resolve serves the three).  sc_dev: frames == nullptr is the
-// 3DSC (normals read; rnd nullable: the stream of seed 12345 from its start), else USC.
+int rift_cap_small();
+// 3D shape contexts, unique shape contexts and SHOT's frames alone (pfx_shape_context.hip).
+// sc_dev: frames == nullptr is the 3DSC (normals read; rnd nullable: the stream of seed 12345 from
+// its start), else USC.
 void sc_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx, const float* sny,
             const float* snz, int64_t ns, const float* qx, const float* qy, const float* qz, const float* frames,
             int64_t nq, double R, double rmin, double rho, const float* rnd, float* desc, float* rf);
 void shot_lrf_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, const float* qx,
                   const float* qy, const float* qz, int64_t nq, double r, float* rf);
-void sc_resolve(pfx_ctx* ctx);
-int sc_cap_small();  // neighbours of the first pass (stat "sc_cap_small")
-// moment invariants and principal curvatures (pfx_moments.hip): stream-ordered, no host
-// synchronisation; errors and statistics as spin images (moments_resolve serves both)
+int sc_cap_small();
+// moment invariants and principal curvatures (pfx_moments.hip)
 void moments_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, const float* qx,
                  const float* qy, const float* qz, int64_t nq, double r, float* out);
 void pcurv_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx, const float* sny,
                const float* snz, int64_t ns, const float* qx, const float* qy, const float* qz, const float* qnx,
                const float* qny, const float* qnz, int64_t nq, double r, float* out);
-void moments_resolve(pfx_ctx* ctx);
-int moments_cap_small();  // neighbours of the first pass (stat "moments_cap_small")
+int moments_cap_small();
 // boost::mt19937 through uniform_01<float>: n floats of the stream of `seed` after `skip` floats
 void rng_uniform01(uint32_t seed, int64_t skip, int64_t n, float* out);
 void range_image_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,

@@ -10,46 +10,22 @@
 // record is the neighbour's xyz (moment invariants) or its normal projected onto the tangent plane
 // of the query normal (principal curvatures: every thread projects its own neighbour, only the
 // chains are serial).  Thread 0 does the closed-form finish.  No floating-point atomic.
-// Both follow spin's two-pass capacity scheme (kMomCapSmall keys, then the queued pass with kMomCap)
-// and report late errors and statistics through pinned memory in stream order (moments_resolve).
+// Both run the two passes of pfx_two_pass.h and report late errors and statistics through the
+// deferred reports (moments_report, pcurv_report; no words of their own).
 // A NaN is written as 0x7fc00000, here and in the restatement.
-#include <cstring>
-
-#include <algorithm>
-#include <string>
-
-#include "pfx_device_math.h"
-#include "pfx_internal.h"
-#include "pfx_neighbors.h"
+#include "pfx_two_pass.h"
 
 namespace pfx {
 namespace {
 
-constexpr int kMomCapSmall = 2048;  // keys of the first pass (bucketed sort: 2 x 16 KiB of LDS)
-constexpr int kMomCap = 16384;      // keys of the second pass (128 KiB: one workgroup per CU)
-constexpr int kMomChunk = 256;      // neighbours per chunk of records = the block size
-
-// err words (ints) of either call.  Sticky until reported: [0] largest k beyond kMomCap.  Per
-// call: [2] queued queries, [3] max k, [4..5] neighbours (u64).
-constexpr int kErrWords = 8;
-struct MomReadback {
-  int mi[kErrWords];
-  int pc[kErrWords];
-};
-
-__device__ __forceinline__ float canon_nan(float v) { return v != v ? __uint_as_float(0x7fc00000u) : v; }
-
-__global__ void k_moments_fill(float* __restrict__ p, int64_t n, float v) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) p[i] = v;
-}
+constexpr int kMomChunk = kTwoPassChunk;
 
 // The 16 KiB behind the keys: the bucketed sort's scratch, then (the sort done) the records.
 struct MomAux {
   float4 rec[kMomChunk];  // x, y, z of the chunk's neighbours, or their projected normals (w unused)
   float acc[12];          // the centroid, then the six sums
 };
-static_assert(sizeof(MomAux) <= sizeof(uint64_t) * kMomCapSmall, "the records fit the sort scratch");
+static_assert(sizeof(MomAux) <= kTwoPassAuxBytes, "the records fit the sort scratch");
 
 // j1 j2 j3 of mu200 mu020 mu002 mu110 mu101 mu011, each expression as C++ parses it
 __device__ __forceinline__ void moments_finish(const float s[6], float o[3]) {
@@ -83,12 +59,6 @@ __device__ __forceinline__ void pcurv_finish(const float s[6], int k, float o[5]
   o[4] = canon_nan(e1 * rk);
 }
 
-// a query with more than CAP neighbours: queued for the second pass, or beyond every capacity
-__device__ __forceinline__ void over_or_err(int k, int64_t q, int32_t* over, int* err) {
-  if (over) over[atomicAdd(err + 2, 1)] = (int32_t)q;
-  else { atomicMax(err, k); atomicMax(err + 3, k); }
-}
-
 // list (nullable): the queued queries with their device-side count; over (nullable): where a query
 // with more than CAP neighbours is queued (else it is beyond every capacity: err[0]).
 // PCURV: snx / sny / snz are the surface normals and qnx / qny / qnz the query normals (else unread).
@@ -117,17 +87,12 @@ __global__ void __launch_bounds__(kMomChunk) k_moments(GridView g, const float* 
   for (int64_t wi = blockIdx.x; wi < count; wi += gridDim.x) {
     const int64_t q = list ? (int64_t)list[wi] : wi;
     // (a non-finite query has no candidate run: k = 0)
-    const int k = CAP == kMomCapSmall
-                      ? sorted_neighbors_bucketed(g, qx[q], qy[q], qz[q], rr, keys, keys + CAP, CAP, &s_count, SB)
-                      : sorted_neighbors(g, qx[q], qy[q], qz[q], rr, keys, CAP, &s_count);
+    const int k = two_pass_neighbors<CAP>(g, qx[q], qy[q], qz[q], rr, keys, &s_count, SB);
     if (k > CAP) {
       if (tid == 0) over_or_err(k, q, over, err);
       continue;
     }
-    if (tid == 0) {
-      atomicAdd(reinterpret_cast<unsigned long long*>(err + 4), (unsigned long long)k);
-      atomicMax(err + 3, k);
-    }
+    if (tid == 0) count_neighbors(k, err);
     if (k == 0) {
       if (tid < W) out[W * q + tid] = nan;
       continue;
@@ -206,69 +171,34 @@ __global__ void __launch_bounds__(kMomChunk) k_moments(GridView g, const float* 
   }
 }
 
-int* err_words(pfx_ctx* ctx, const char* name) {
-  DevBuf& eb = ctx->buf(name);
-  const bool fresh = !eb.ptr;
-  int* err = eb.as<int>(kErrWords);
-  if (fresh) PFX_HIP(hipMemsetAsync(err, 0, 2 * sizeof(int), ctx->stream));               // the sticky words
-  PFX_HIP(hipMemsetAsync(err + 2, 0, (kErrWords - 2) * sizeof(int), ctx->stream));  // the per-call words
-  return err;
-}
-
-// the surface grid prepared ahead (pfx_fpfh_prepare_dev: coordinates only), else built here
-GridView feature_grid(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, double r) {
-  const bool grid_ready = ctx->prep_x == sx && ctx->prep_n == ns && ctx->prep_r == r;
-  if (grid_ready) fpfh_validate_grid(ctx);  // (a speculative prepared grid: exact after this)
-  ctx->prep_x = nullptr;  // one-shot
-  ctx->prep_n = -1;
-  ctx->prep_qx = nullptr;
-  ctx->prep_nq = -1;
-  if (!grid_ready) build_grid(ctx, ctx->grid_b, sx, sy, sz, ns, r);
-  return view(ctx->grid_b);
-}
-
-constexpr size_t kAuxBytes = sizeof(uint64_t) * kMomCapSmall;
-constexpr size_t kLdsSmall = sizeof(uint64_t) * kMomCapSmall + kAuxBytes;
-constexpr size_t kLdsLarge = sizeof(uint64_t) * kMomCap + kAuxBytes;
-
 template <bool PCURV>
 void launch(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx, const float* sny,
             const float* snz, int64_t ns, const float* qx, const float* qy, const float* qz, const float* qnx,
             const float* qny, const float* qnz, int64_t nq, double r, float* out) {
   if (nq == 0) return;
   constexpr int W = PCURV ? 5 : 3;
+  constexpr ReportSlot slot = PCURV ? kRepPcurv : kRepMoments;
   hipStream_t st = ctx->stream;
-  int* err = err_words(ctx, PCURV ? "pcurv_err" : "moments_err");
+  int* err = report_words(ctx, slot);
   if (ns == 0) {  // every k is 0
-    k_moments_fill<<<(unsigned)ceil_div(W * nq, 256), 256, 0, st>>>(out, W * nq, __builtin_nanf(""));
-    check_launch("k_moments_fill");
+    fill_nan(ctx, out, W * nq);
   } else {
     const GridView g = feature_grid(ctx, sx, sy, sz, ns, r);
-    // a neighbourhood can only outgrow the first pass when the surface has more points than that
-    const bool second_pass = ns > kMomCapSmall;
-    int32_t* over = second_pass ? ctx->buf(PCURV ? "pcurv_over" : "moments_over").as<int32_t>((size_t)nq) : nullptr;
     const float rr = (float)(r * r);
     TimeScope ts(ctx, PCURV ? "principal_curvatures" : "moment_invariants", true);
-    k_moments<kMomCapSmall, PCURV><<<(unsigned)std::min<int64_t>(nq, 1 << 20), kMomChunk, kLdsSmall, st>>>(
-        g, snx, sny, snz, qx, qy, qz, qnx, qny, qnz, nq, rr, nullptr, nullptr, over, out, err);
-    if (second_pass) {
-      PFX_HIP(hipFuncSetAttribute((const void*)k_moments<kMomCap, PCURV>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLarge));
-      // longer lists: the count stays on the device
-      k_moments<kMomCap, PCURV><<<(unsigned)std::min<int64_t>(nq, 256), kMomChunk, kLdsLarge, st>>>(
-          g, snx, sny, snz, qx, qy, qz, qnx, qny, qnz, nq, rr, over, err + 2, nullptr, out, err);
-    }
+    two_pass(ctx, ns, nq, PCURV ? "pcurv_over" : "moments_over", err,
+             [&](auto cap, unsigned blocks, size_t lds, const int32_t* list, const int* n_list, int32_t* over) {
+               two_pass_launch(k_moments<cap(), PCURV>, blocks, lds, st, g, snx, sny, snz, qx, qy, qz, qnx, qny, qnz,
+                               nq, rr, list, n_list, over, out, err);
+             });
     check_launch("k_moments");
   }
-  if (!ctx->moments_rb_mem) PFX_HIP(hipHostMalloc(&ctx->moments_rb_mem, sizeof(MomReadback), hipHostMallocDefault));
-  MomReadback* rb = static_cast<MomReadback*>(ctx->moments_rb_mem);
-  PFX_HIP(hipMemcpyAsync(PCURV ? rb->pc : rb->mi, err, sizeof(int) * kErrWords, hipMemcpyDeviceToHost, st));
-  (PCURV ? ctx->pcurv_pending : ctx->moments_pending) = true;
+  report_post(ctx, slot, err);
 }
 
 }  // namespace
 
-int moments_cap_small() { return kMomCapSmall; }
+int moments_cap_small() { return kTwoPassCapSmall; }
 
 void moments_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, const float* qx,
                  const float* qy, const float* qz, int64_t nq, double r, float* out) {
@@ -281,30 +211,7 @@ void pcurv_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, 
   launch<true>(ctx, sx, sy, sz, snx, sny, snz, ns, qx, qy, qz, qnx, qny, qnz, nq, r, out);
 }
 
-// After a synchronisation of ctx's stream: the last moments_dev's and pcurv_dev's statistics and
-// their capacity errors, each reported once.
-void moments_resolve(pfx_ctx* ctx) {
-  for (int which = 0; which < 2; ++which) {
-    bool& pending = which ? ctx->pcurv_pending : ctx->moments_pending;
-    if (!pending) continue;
-    pending = false;
-    const MomReadback* rb = static_cast<const MomReadback*>(ctx->moments_rb_mem);
-    const int* h = which ? rb->pc : rb->mi;
-    unsigned long long nb;
-    std::memcpy(&nb, h + 4, sizeof(nb));
-    const std::string name = which ? "pcurv" : "moments";
-    ctx->stats[name + "_neighbors"] = (int64_t)nb;
-    ctx->stats[name + "_kmax"] = h[3];
-    ctx->stats[name + "_queued"] = h[2];
-    if (h[0] > 0) {
-      const int cap = h[0];
-      int* err = ctx->buf(which ? "pcurv_err" : "moments_err").as<int>(kErrWords);
-      PFX_HIP(hipMemsetAsync(err, 0, 2 * sizeof(int), ctx->stream));  // reported once
-      throw Error(PFX_ERR_CAPACITY, (which ? "principal_curvatures" : "moment_invariants") +
-                                        std::string(": a query has ") + std::to_string(cap) + " neighbours (> " +
-                                        std::to_string(kMomCap) + " supported)");
-    }
-  }
-}
+void moments_report(pfx_ctx* ctx, const int* h) { two_pass_report(ctx, h, "moments", "moment_invariants"); }
+void pcurv_report(pfx_ctx* ctx, const int* h) { two_pass_report(ctx, h, "pcurv", "principal_curvatures"); }
 
 }  // namespace pfx

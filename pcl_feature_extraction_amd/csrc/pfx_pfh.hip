@@ -13,7 +13,7 @@
 // path of the pair features, exact path where that cannot decide).  Longer neighbourhoods are
 // queued for a second pass whose records live in a per-workgroup slice of a ctx-owned global
 // scratch buffer (k <= kPfhMaxK, where the pair count still fits 32 bits); beyond that the row is
-// NaN and PFX_ERR_CAPACITY is reported after the next synchronisation (pfh_resolve).
+// NaN and PFX_ERR_CAPACITY is reported after the next synchronisation (pfh_report).
 #include <cstring>
 
 #include "pfx_neighbors.h"
@@ -43,15 +43,6 @@ constexpr int kCopies = 2 * (kPT / 64);  // counter copies: two per wave (lane p
 constexpr int kCntStride = 128;      // ints per counter copy (125 used)
 constexpr int kHeadInts = kCopies * kCntStride + 2 * (kPT / 64);  // counters + the gather's wave counts
 static_assert(kHeadInts % 4 == 0, "the records that follow are float4");
-
-struct PfhReadback {  // err words of the last call, copied to pinned memory in stream order
-  int h[6];
-};
-
-__global__ void k_pfh_nan_rows(float* __restrict__ out, int64_t n) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i < n) out[i] = __builtin_nanf("");
-}
 
 // the exact path out of line (rare once the fast path is on): h1 + 5 h2 + 25 h3, or -1 for a pair
 // computePairFeatures rejects
@@ -226,25 +217,13 @@ void pfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, co
   PFX_CHECK(r > 0.0, "pfh: radius must be > 0");
   if (nq == 0) return;
   hipStream_t st = ctx->stream;
-  DevBuf& eb = ctx->buf("pfh_err");
-  const bool fresh = !eb.ptr;
-  int* err = eb.as<int>(6);
-  if (fresh) PFX_HIP(hipMemsetAsync(err, 0, sizeof(int), st));  // the sticky word starts clear
-  PFX_HIP(hipMemsetAsync(err + 1, 0, 5 * sizeof(int), st));     // the per-call words
+  int* err = report_words(ctx, kRepPfh);  // [0] sticky, [1..5] per call (pfh_report)
   if (ns == 0) {
     // no surface: every query has an empty neighbourhood -> NaN rows (PCL fills NaN)
-    k_pfh_nan_rows<<<(unsigned)ceil_div(nq * kDesc, 256), 256, 0, st>>>(out, nq * kDesc);
-    check_launch("k_pfh_nan_rows");
+    k_fill<<<(unsigned)ceil_div(nq * kDesc, 256), 256, 0, st>>>(out, nq * kDesc, __builtin_nanf(""));
+    check_launch("k_fill");
   } else {
-    // the surface grid prepared ahead (pfx_fpfh_prepare_dev: coordinates only), else built here
-    const bool grid_ready = ctx->prep_x == sx && ctx->prep_n == ns && ctx->prep_r == r;
-    if (grid_ready) fpfh_validate_grid(ctx);  // (a speculative prepared grid: exact after this)
-    ctx->prep_x = nullptr;  // one-shot
-    ctx->prep_n = -1;
-    ctx->prep_qx = nullptr;
-    ctx->prep_nq = -1;
-    if (!grid_ready) build_grid(ctx, ctx->grid_b, sx, sy, sz, ns, r);
-    const GridView g = view(ctx->grid_b);
+    const GridView g = feature_grid(ctx, sx, sy, sz, ns, r);
     const float rr = (float)(r * r);
     // a neighbourhood can only outgrow the LDS records when the surface has more points than that
     const bool overflow_pass = ns > kPfhCapLds;
@@ -270,30 +249,19 @@ void pfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, co
                                                                                                  out);
     check_launch("k_pfh");
   }
-  // statistics and the sticky error word land in pinned memory in stream order; no host
-  // synchronisation here
-  if (!ctx->pfh_rb_mem) PFX_HIP(hipHostMalloc(&ctx->pfh_rb_mem, sizeof(PfhReadback), hipHostMallocDefault));
-  PFX_HIP(hipMemcpyAsync(ctx->pfh_rb_mem, err, sizeof(PfhReadback), hipMemcpyDeviceToHost, st));
-  ctx->pfh_pending = true;
+  report_post(ctx, kRepPfh, err);
 }
 
-// After a synchronisation of ctx's stream: the last pfh_dev's statistics, and its capacity check
-// (PFX_ERR_CAPACITY, reported here for the stream-ordered API; the host API calls this at once).
-void pfh_resolve(pfx_ctx* ctx) {
-  if (!ctx->pfh_pending) return;
-  ctx->pfh_pending = false;
-  const int* h = static_cast<const PfhReadback*>(ctx->pfh_rb_mem)->h;
+// The last pfh_dev's statistics, and its capacity check (PFX_ERR_CAPACITY).
+void pfh_report(pfx_ctx* ctx, const int* h) {
   unsigned long long pr;
   std::memcpy(&pr, h + 2, sizeof(pr));
   ctx->stats["pfh_pairs"] = (int64_t)pr;
   ctx->stats["pfh_global"] = h[1];
   ctx->stats["pfh_kmax"] = h[4];
-  if (h[0] > 0) {
-    int* err = ctx->buf("pfh_err").as<int>(6);
-    PFX_HIP(hipMemsetAsync(err, 0, sizeof(int), ctx->stream));  // reported once
+  if (h[0] > 0)
     throw Error(PFX_ERR_CAPACITY, "pfh: a query has " + std::to_string(h[0]) + " neighbours (> " +
                                       std::to_string(kPfhMaxK) + " supported)");
-  }
 }
 
 }  // namespace pfx

@@ -19,44 +19,26 @@
 // in ascending order and adds them, its float accumulator in a register for the whole query.  No
 // floating-point atomic.  (Every bin walking every record of the chunk instead took 1.9 times as
 // long: DESIGN.md.)  The squared norm follows Eigen 3.2's float order (pfx_eigen_redux.h).
-// Both follow spin's two-pass capacity scheme (kRiftCapSmall keys, then the queued pass with
-// kRiftCap) and report late errors and statistics through pinned memory in stream order
-// (rift_resolve).  A NaN is written as 0x7fc00000, here and in the restatement.
+// Both run the two passes of pfx_two_pass.h and report late errors and statistics through the
+// deferred reports (igrad_report, rift_report; no words of their own).  A NaN is written as
+// 0x7fc00000, here and in the restatement.
 #include <cfloat>
 #include <cmath>
 #include <cstring>
 
-#include <algorithm>
 #include <string>
 
 #include "pfx_eigen6.h"
 #include "pfx_eigen_redux.h"
 #include "pfx_nblist.h"
-#include "pfx_neighbors.h"
+#include "pfx_two_pass.h"
 
 namespace pfx {
 namespace {
 
-constexpr int kRiftCapSmall = 2048;  // keys of the first pass (bucketed sort: 2 x 16 KiB of LDS)
-constexpr int kRiftCap = 16384;      // keys of the second pass (128 KiB: one workgroup per CU)
-constexpr int kRiftChunk = 256;      // neighbours per chunk of records = the block size
+constexpr int kRiftChunk = kTwoPassChunk;
 constexpr int kRiftMaxBins = 16;     // per axis
 constexpr int kNoCol = 31;           // a record's unused column slot (no bin has this column)
-
-// err words (ints) of either call.  Sticky until reported: [0] largest k beyond kRiftCap.  Per
-// call: [2] queued queries, [3] max k, [4..5] neighbours (u64).
-constexpr int kErrWords = 8;
-struct RiftReadback {
-  int ig[kErrWords];
-  int rf[kErrWords];
-};
-
-__device__ __forceinline__ float canon_nan(float v) { return v != v ? __uint_as_float(0x7fc00000u) : v; }
-
-__global__ void k_rift_fill(float* __restrict__ p, int64_t n, float v) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) p[i] = v;
-}
 
 // x = colPivHouseholderQr(A).solve(b), gradient = (Identity - n n^T) x
 __device__ __forceinline__ void igrad_finish(const float s[9], const float nv[3], float o[3]) {
@@ -166,8 +148,8 @@ __global__ void __launch_bounds__(256) k_igrad_lists(GridView g, NbLists L, cons
   }
   __syncthreads();
   if (tid == 0 && s_sum) {
-    atomicAdd(reinterpret_cast<unsigned long long*>(err + 4), s_sum);
-    atomicMax(err + 3, s_max);
+    atomicAdd(reinterpret_cast<unsigned long long*>(err + kWordNeighbors), s_sum);
+    atomicMax(err + kWordKmax, s_max);
   }
 }
 
@@ -176,12 +158,6 @@ struct IgradAux {
   float4 rec[kRiftChunk];  // x, y, z, I of the chunk's neighbours
   float acc[16];           // centroid and mean, then the nine sums
 };
-
-// a query with more than CAP neighbours: queued for the second pass, or beyond every capacity
-__device__ __forceinline__ void over_or_err(int k, int64_t q, int32_t* over, int* err) {
-  if (over) over[atomicAdd(err + 2, 1)] = (int32_t)q;
-  else { atomicMax(err, k); atomicMax(err + 3, k); }
-}
 
 // list (nullable): the queued queries with their device-side count; over (nullable): where a query
 // with more than CAP neighbours is queued (else it is beyond every capacity: err[0]).
@@ -207,17 +183,12 @@ __global__ void __launch_bounds__(kRiftChunk) k_igrad_query(GridView g, const fl
   for (int64_t wi = blockIdx.x; wi < count; wi += gridDim.x) {
     const int64_t q = list ? (int64_t)list[wi] : wi;
     // (a non-finite query has no candidate run: k = 0)
-    const int k = CAP == kRiftCapSmall
-                      ? sorted_neighbors_bucketed(g, qx[q], qy[q], qz[q], rr, keys, keys + CAP, CAP, &s_count, SB)
-                      : sorted_neighbors(g, qx[q], qy[q], qz[q], rr, keys, CAP, &s_count);
+    const int k = two_pass_neighbors<CAP>(g, qx[q], qy[q], qz[q], rr, keys, &s_count, SB);
     if (k > CAP) {
       if (tid == 0) over_or_err(k, q, over, err);
       continue;
     }
-    if (tid == 0) {
-      atomicAdd(reinterpret_cast<unsigned long long*>(err + 4), (unsigned long long)k);
-      atomicMax(err + 3, k);
-    }
+    if (tid == 0) count_neighbors(k, err);
     if (k < 3) {
       if (tid < 3) out[3 * q + tid] = nan;
       continue;
@@ -284,8 +255,8 @@ struct RiftAux {
   float inv;
   unsigned long long mask[2][2 * kRiftMaxBins][kRiftChunk / 64];  // rows 0..15 distance bins, 16..31 columns
 };
-static_assert(sizeof(RiftAux) <= sizeof(uint64_t) * kRiftCapSmall, "the records fit the sort scratch");
-static_assert(sizeof(IgradAux) <= sizeof(uint64_t) * kRiftCapSmall, "the records fit the sort scratch");
+static_assert(sizeof(RiftAux) <= kTwoPassAuxBytes, "the records fit the sort scratch");
+static_assert(sizeof(IgradAux) <= kTwoPassAuxBytes, "the records fit the sort scratch");
 
 template <int CAP>
 __global__ void __launch_bounds__(kRiftChunk) k_rift(GridView g, const float* __restrict__ sgx,
@@ -308,17 +279,12 @@ __global__ void __launch_bounds__(kRiftChunk) k_rift(GridView g, const float* __
   for (int64_t wi = blockIdx.x; wi < count; wi += gridDim.x) {
     const int64_t q = list ? (int64_t)list[wi] : wi;
     const float cx = qx[q], cy = qy[q], cz = qz[q];
-    const int k = CAP == kRiftCapSmall
-                      ? sorted_neighbors_bucketed(g, cx, cy, cz, rr, keys, keys + CAP, CAP, &s_count, SB)
-                      : sorted_neighbors(g, cx, cy, cz, rr, keys, CAP, &s_count);
+    const int k = two_pass_neighbors<CAP>(g, cx, cy, cz, rr, keys, &s_count, SB);
     if (k > CAP) {
       if (tid == 0) over_or_err(k, q, over, err);
       continue;
     }
-    if (tid == 0) {
-      atomicAdd(reinterpret_cast<unsigned long long*>(err + 4), (unsigned long long)k);
-      atomicMax(err + 3, k);
-    }
+    if (tid == 0) count_neighbors(k, err);
     if (k == 0) {  // (PCL leaves the previous query's matrix: a deliberate deviation)
       if (tid < S) out[q * S + tid] = __uint_as_float(0x7fc00000u);
       continue;
@@ -394,47 +360,9 @@ __global__ void __launch_bounds__(kRiftChunk) k_rift(GridView g, const float* __
   }
 }
 
-int* err_words(pfx_ctx* ctx, const char* name) {
-  DevBuf& eb = ctx->buf(name);
-  const bool fresh = !eb.ptr;
-  int* err = eb.as<int>(kErrWords);
-  if (fresh) PFX_HIP(hipMemsetAsync(err, 0, 2 * sizeof(int), ctx->stream));               // the sticky words
-  PFX_HIP(hipMemsetAsync(err + 2, 0, (kErrWords - 2) * sizeof(int), ctx->stream));  // the per-call words
-  return err;
-}
-
-// the surface grid prepared ahead (pfx_fpfh_prepare_dev: coordinates only), else built here
-GridView feature_grid(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, double r) {
-  const bool grid_ready = ctx->prep_x == sx && ctx->prep_n == ns && ctx->prep_r == r;
-  if (grid_ready) fpfh_validate_grid(ctx);  // (a speculative prepared grid: exact after this)
-  ctx->prep_x = nullptr;  // one-shot
-  ctx->prep_n = -1;
-  ctx->prep_qx = nullptr;
-  ctx->prep_nq = -1;
-  if (!grid_ready) build_grid(ctx, ctx->grid_b, sx, sy, sz, ns, r);
-  return view(ctx->grid_b);
-}
-
-void readback(pfx_ctx* ctx, const int* err, bool rift) {
-  if (!ctx->rift_rb_mem) PFX_HIP(hipHostMalloc(&ctx->rift_rb_mem, sizeof(RiftReadback), hipHostMallocDefault));
-  RiftReadback* rb = static_cast<RiftReadback*>(ctx->rift_rb_mem);
-  PFX_HIP(hipMemcpyAsync(rift ? rb->rf : rb->ig, err, sizeof(int) * kErrWords, hipMemcpyDeviceToHost, ctx->stream));
-  (rift ? ctx->rift_pending : ctx->igrad_pending) = true;
-}
-
-void fill_nan(pfx_ctx* ctx, float* p, int64_t n) {
-  if (n <= 0) return;
-  k_rift_fill<<<(unsigned)ceil_div(n, 256), 256, 0, ctx->stream>>>(p, n, __builtin_nanf(""));
-  check_launch("k_rift_fill");
-}
-
-constexpr size_t kAuxBytes = sizeof(uint64_t) * kRiftCapSmall;
-constexpr size_t kLdsSmall = sizeof(uint64_t) * kRiftCapSmall + kAuxBytes;
-constexpr size_t kLdsLarge = sizeof(uint64_t) * kRiftCap + kAuxBytes;
-
 }  // namespace
 
-int rift_cap_small() { return kRiftCapSmall; }
+int rift_cap_small() { return kTwoPassCapSmall; }
 
 void igrad_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* si, int64_t ns,
                const float* qx, const float* qy, const float* qz, const float* qnx, const float* qny,
@@ -449,36 +377,31 @@ void igrad_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, 
     float* cv = ctx->buf("ig_cv").as<float>(ns);
     normals_lists_dev(ctx, sx, sy, sz, ns, r, nx, ny, nz, cv);
     const NbLists& L = ctx->normals->L;
-    int* err = err_words(ctx, "igrad_err");
+    int* err = report_words(ctx, kRepIgrad);
     fill_nan(ctx, out, 3 * ns);  // points off the lists (non-finite) keep a NaN row
     if (L.nq > 0) {
       TimeScope ts(ctx, "intensity_gradient_cloud", true);
       k_igrad_lists<<<(unsigned)ceil_div(L.nq, 256), 256, 0, st>>>(view(ctx->grid_a), L, si, qnx, qny, qnz, out, err);
       check_launch("k_igrad_lists");
     }
-    readback(ctx, err, false);
+    report_post(ctx, kRepIgrad, err);
     return;
   }
-  int* err = err_words(ctx, "igrad_err");
+  int* err = report_words(ctx, kRepIgrad);
   if (ns == 0) {
     fill_nan(ctx, out, 3 * nq);
   } else {
     const GridView g = feature_grid(ctx, sx, sy, sz, ns, r);
-    const bool second_pass = ns > kRiftCapSmall;
-    int32_t* over = second_pass ? ctx->buf("igrad_over").as<int32_t>((size_t)nq) : nullptr;
     const float rr = (float)(r * r);
     TimeScope ts(ctx, "intensity_gradient", true);
-    k_igrad_query<kRiftCapSmall><<<(unsigned)std::min<int64_t>(nq, 1 << 20), kRiftChunk, kLdsSmall, st>>>(
-        g, si, qx, qy, qz, qnx, qny, qnz, nq, rr, nullptr, nullptr, over, out, err);
-    if (second_pass) {
-      PFX_HIP(hipFuncSetAttribute((const void*)k_igrad_query<kRiftCap>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)kLdsLarge));
-      k_igrad_query<kRiftCap><<<(unsigned)std::min<int64_t>(nq, 256), kRiftChunk, kLdsLarge, st>>>(
-          g, si, qx, qy, qz, qnx, qny, qnz, nq, rr, over, err + 2, nullptr, out, err);
-    }
+    two_pass(ctx, ns, nq, "igrad_over", err,
+             [&](auto cap, unsigned blocks, size_t lds, const int32_t* list, const int* n_list, int32_t* over) {
+               two_pass_launch(k_igrad_query<cap()>, blocks, lds, st, g, si, qx, qy, qz, qnx, qny, qnz, nq, rr, list,
+                               n_list, over, out, err);
+             });
     check_launch("k_igrad_query");
   }
-  readback(ctx, err, false);
+  report_post(ctx, kRepIgrad, err);
 }
 
 void rift_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* sgx, const float* sgy,
@@ -486,54 +409,25 @@ void rift_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, c
               int D, int G, float* out) {
   if (nq == 0) return;
   hipStream_t st = ctx->stream;
-  int* err = err_words(ctx, "rift_err");
+  int* err = report_words(ctx, kRepRift);
   if (ns == 0) {
     fill_nan(ctx, out, nq * D * G);
   } else {
     const GridView g = feature_grid(ctx, sx, sy, sz, ns, r);
-    // a neighbourhood can only outgrow the first pass when the surface has more points than that
-    const bool second_pass = ns > kRiftCapSmall;
-    int32_t* over = second_pass ? ctx->buf("rift_over").as<int32_t>((size_t)nq) : nullptr;
     const float rr = (float)(r * r), rad = (float)r;
     TimeScope ts(ctx, "rift", true);
-    k_rift<kRiftCapSmall><<<(unsigned)std::min<int64_t>(nq, 1 << 20), kRiftChunk, kLdsSmall, st>>>(
-        g, sgx, sgy, sgz, cx, cy, cz, nq, rr, rad, D, G, nullptr, nullptr, over, out, err);
-    if (second_pass) {
-      PFX_HIP(hipFuncSetAttribute((const void*)k_rift<kRiftCap>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)kLdsLarge));
-      // longer lists: the count stays on the device
-      k_rift<kRiftCap><<<(unsigned)std::min<int64_t>(nq, 256), kRiftChunk, kLdsLarge, st>>>(
-          g, sgx, sgy, sgz, cx, cy, cz, nq, rr, rad, D, G, over, err + 2, nullptr, out, err);
-    }
+    two_pass(ctx, ns, nq, "rift_over", err,
+             [&](auto cap, unsigned blocks, size_t lds, const int32_t* list, const int* n_list, int32_t* over) {
+               two_pass_launch(k_rift<cap()>, blocks, lds, st, g, sgx, sgy, sgz, cx, cy, cz, nq, rr, rad, D, G, list,
+                               n_list, over, out, err);
+             });
     check_launch("k_rift");
   }
-  readback(ctx, err, true);
+  report_post(ctx, kRepRift, err);
 }
 
-// After a synchronisation of ctx's stream: the last igrad_dev's and rift_dev's statistics and
-// their capacity errors, each reported once.
-void rift_resolve(pfx_ctx* ctx) {
-  for (int which = 0; which < 2; ++which) {
-    bool& pending = which ? ctx->rift_pending : ctx->igrad_pending;
-    if (!pending) continue;
-    pending = false;
-    const RiftReadback* rb = static_cast<const RiftReadback*>(ctx->rift_rb_mem);
-    const int* h = which ? rb->rf : rb->ig;
-    unsigned long long nb;
-    std::memcpy(&nb, h + 4, sizeof(nb));
-    const std::string name = which ? "rift" : "igrad";
-    ctx->stats[name + "_neighbors"] = (int64_t)nb;
-    ctx->stats[name + "_kmax"] = h[3];
-    if (which) ctx->stats["rift_queued"] = h[2];
-    if (h[0] > 0) {
-      const int cap = h[0];
-      int* err = ctx->buf(which ? "rift_err" : "igrad_err").as<int>(kErrWords);
-      PFX_HIP(hipMemsetAsync(err, 0, 2 * sizeof(int), ctx->stream));  // reported once
-      throw Error(PFX_ERR_CAPACITY, (which ? "rift" : "intensity_gradient") + std::string(": a query has ") +
-                                        std::to_string(cap) + " neighbours (> " + std::to_string(kRiftCap) +
-                                        " supported)");
-    }
-  }
-}
+// (the stat "igrad_queued" has never been written)
+void igrad_report(pfx_ctx* ctx, const int* h) { two_pass_report(ctx, h, "igrad", "intensity_gradient", false); }
+void rift_report(pfx_ctx* ctx, const int* h) { two_pass_report(ctx, h, "rift", "rift"); }
 
 }  // namespace pfx

@@ -8,8 +8,7 @@
 //   k_sc_density    one wave per support point: the number of surface points in its rho-ball, a
 //                   box scan of the grid's cells that the ball can reach (integer, order-free);
 //   k_shape_context one 256-thread workgroup per query:
-//     1. radius neighbours in FLANN order, the keys in LDS (the bucketed sort for
-//        k <= kScCapSmall, longer lists queued for a second pass with kScCap keys);
+//     1. radius neighbours in FLANN order, the keys in LDS (pfx_two_pass.h: the two passes);
 //     2. the frame: the caller's (USC), or the nearest neighbour's normal with the row's three
 //        floats of the random stream, orthogonalised (3DSC; the row's place in the stream is the
 //        number of earlier drawing rows, an exclusive scan of k_sc_mark's flags);
@@ -21,7 +20,7 @@
 //        order.  No floating-point atomic.
 //   k_sc_lrf        one workgroup per query: sorted neighbours, then pfx_shot_core.h's shot_lrf,
 //                   shot_eigen and shot_frame, the frame alone.
-// Stream-ordered: errors and statistics go to pinned memory in stream order (sc_resolve).
+// Stream-ordered: errors and statistics go through the deferred reports (sc_report, lrf_report).
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -29,27 +28,20 @@
 #include <random>
 
 #include "pfx_shot_core.h"
+#include "pfx_two_pass.h"
 
 namespace pfx {
 namespace {
 
-constexpr int kScCapSmall = 2048;  // keys of the first pass (bucketed sort: 2 x 16 KiB of LDS)
-constexpr int kScCap = 16384;      // keys of the second pass (128 KiB: one workgroup per CU)
-constexpr int kScChunk = 256;      // neighbours per chunk of records = the block size
+constexpr int kScChunk = kTwoPassChunk;
 constexpr int kScWords = kScChunk / 64;
 constexpr int kScAz = 12, kScEl = 11, kScRad = 15;  // PCL 1.7's fixed bins
 constexpr int kScLen = kScAz * kScEl * kScRad;     // 1980
 
-// err words (ints).  Sticky until reported: [0] largest k beyond kScCap.  Per call: [2] queued
-// queries, [3] max k, [4..5] neighbours (u64), [6] drawing rows, [7] neighbours skipped as too
-// close, [8] support points.
-constexpr int kErrWords = 12;
-// the frames' words: [0] sticky largest k beyond kCap, [1] queued queries
-constexpr int kLrfWords = 4;
-struct ScReadback {
-  int sc[kErrWords];
-  int lrf[kLrfWords];
-};
+// The shape contexts' own words (per call): the drawing rows, the neighbours skipped as too close,
+// the support points.  The frames have none, and no statistics.
+constexpr int kWordDraws = kWordOwn, kWordSkipped = kWordOwn + 1, kWordSupport = kWordOwn + 2;
+static_assert(kCapSmall == kTwoPassCapSmall && kCap == kTwoPassCap, "k_sc_lrf: SHOT's capacities are the frame's");
 
 // built on the host (the C library's cosf, powf, exp and log: the restatement's), read from LDS
 struct ScTables {
@@ -84,7 +76,6 @@ __global__ void k_sc_tables(ScTables T, float* __restrict__ out) {
   for (int i = threadIdx.x; i < kTableWords; i += blockDim.x) out[i] = src[i];
 }
 
-__device__ __forceinline__ float canon_nan(float v) { return v != v ? __uint_as_float(0x7fc00000u) : v; }
 __device__ __forceinline__ bool sc_equal(float a, float b) { return fabsf(a - b) < FLT_EPSILON; }
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
@@ -117,7 +108,7 @@ __global__ void __launch_bounds__(256) k_sc_mark(GridView g, const float* __rest
       any = __syncthreads_or(any);
       if (threadIdx.x == 0) {
         draws[q] = any;
-        if (any) atomicAdd(err + 6, 1);
+        if (any) atomicAdd(err + kWordDraws, 1);
       }
     }
   }
@@ -177,7 +168,7 @@ __global__ void __launch_bounds__(256) k_sc_density(GridView gs, const uint8_t* 
       if (lane == 0) dens[gs.perm[base + b]] = c;
     }
   }
-  if (lane == 0 && nsup) atomicAdd(err + 8, nsup);
+  if (lane == 0 && nsup) atomicAdd(err + kWordSupport, nsup);
 }
 
 // The 16 KiB behind the keys: the bucketed sort's scratch, then (the sort done) the chunk's records
@@ -187,13 +178,7 @@ struct ScAux {
   int bin[kScChunk];
   float w[kScChunk];
 };
-static_assert(sizeof(ScAux) <= sizeof(uint64_t) * kScCapSmall, "the records fit the sort scratch");
-
-__device__ __forceinline__ void over_or_err(int k, int64_t q, int32_t* over, int* err) {
-  if (over) over[atomicAdd(err + 2, 1)] = (int32_t)q;
-  else atomicMax(err, k);
-  atomicMax(err + 3, k);
-}
+static_assert(sizeof(ScAux) <= kTwoPassAuxBytes, "the records fit the sort scratch");
 
 // list (nullable): the queued queries with their device-side count; over (nullable): where a query
 // with more than CAP neighbours is queued (else it is beyond every capacity: err[0]).
@@ -229,17 +214,12 @@ __global__ void __launch_bounds__(kScChunk) k_shape_context(
       sc_fill(d, rfo, __uint_as_float(0x7fc00000u), nullptr);
       continue;
     }
-    const int k = CAP == kScCapSmall
-                      ? sorted_neighbors_bucketed(g, cx, cy, cz, rr, keys, keys + CAP, CAP, &s_count, SB)
-                      : sorted_neighbors(g, cx, cy, cz, rr, keys, CAP, &s_count);
+    const int k = two_pass_neighbors<CAP>(g, cx, cy, cz, rr, keys, &s_count, SB);
     if (k > CAP) {
       if (tid == 0) over_or_err(k, q, over, err);
       continue;
     }
-    if (tid == 0) {
-      atomicAdd(reinterpret_cast<unsigned long long*>(err + 4), (unsigned long long)k);
-      atomicMax(err + 3, k);
-    }
+    if (tid == 0) count_neighbors(k, err);
     if (k == 0) {  // 3DSC: NaN, no frame, no draw; USC: an empty histogram in the caller's frame
       sc_fill(d, rfo, USC ? 0.0f : __uint_as_float(0x7fc00000u), frame);
       continue;
@@ -322,7 +302,7 @@ __global__ void __launch_bounds__(kScChunk) k_shape_context(
     }
     for (int i = tid; i < kScLen; i += kScChunk) d[i] = acc[i];
     if (tid < 9) rfo[tid] = canon_nan(s_rf[tid]);
-    if (tid == 0 && s_skip) atomicAdd(err + 7, s_skip);
+    if (tid == 0 && s_skip) atomicAdd(err + kWordSkipped, s_skip);
     __syncthreads();  // acc, s_rf and A are read before the next query overwrites them
   }
 }
@@ -362,14 +342,9 @@ __global__ void __launch_bounds__(256) k_sc_lrf(GridView g, const float* __restr
       if (tid < 9) rfo[tid] = __builtin_nanf("");
       continue;
     }
-    const int k = CAP == kCapSmall
-                      ? sorted_neighbors_bucketed(g, cx, cy, cz, rr, keys, keys + CAP, CAP, &s_count, SB)
-                      : sorted_neighbors(g, cx, cy, cz, rr, keys, CAP, &s_count);
+    const int k = two_pass_neighbors<CAP>(g, cx, cy, cz, rr, keys, &s_count, SB);
     if (k > CAP) {
-      if (tid == 0) {
-        if (over) over[atomicAdd(err + 1, 1)] = (int32_t)q;
-        else atomicMax(err, k);
-      }
+      if (tid == 0) over_or_err<false>(k, q, over, err);
       continue;
     }
     const NbKeys src{keys, g.ux, g.uy, g.uz, nullptr, nullptr, nullptr, cx, cy, cz};
@@ -393,28 +368,6 @@ __global__ void __launch_bounds__(256) k_sc_lrf(GridView g, const float* __restr
   }
 }
 
-__global__ void k_sc_fill(float* __restrict__ p, int64_t n, float v) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
-}
-
-// the surface grid prepared ahead (pfx_fpfh_prepare_dev: coordinates only), else built here
-GridView feature_grid(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, double r) {
-  const bool grid_ready = ctx->prep_x == sx && ctx->prep_n == ns && ctx->prep_r == r;
-  if (grid_ready) fpfh_validate_grid(ctx);  // (a speculative prepared grid: exact after this)
-  ctx->prep_x = nullptr;  // one-shot
-  ctx->prep_n = -1;
-  ctx->prep_qx = nullptr;
-  ctx->prep_nq = -1;
-  if (!grid_ready) build_grid(ctx, ctx->grid_b, sx, sy, sz, ns, r);
-  return view(ctx->grid_b);
-}
-
-ScReadback* sc_rb(pfx_ctx* ctx) {
-  if (!ctx->sc_rb_mem) PFX_HIP(hipHostMalloc(&ctx->sc_rb_mem, sizeof(ScReadback), hipHostMallocDefault));
-  return static_cast<ScReadback*>(ctx->sc_rb_mem);
-}
-
 float next_uniform01(std::mt19937& eng) {
   for (;;) {
     const float v = (float)(uint32_t)eng() * (1.0f / 4294967296.0f);
@@ -422,34 +375,22 @@ float next_uniform01(std::mt19937& eng) {
   }
 }
 
-constexpr size_t kAuxBytes = sizeof(uint64_t) * kScCapSmall;
-constexpr size_t kLdsSmall = sizeof(uint64_t) * kScCapSmall + kAuxBytes;
-constexpr size_t kLdsLarge = sizeof(uint64_t) * kScCap + kAuxBytes;
-
 template <bool USC>
 void sc_launch(pfx_ctx* ctx, const GridView& g, const float* snx, const float* sny, const float* snz, int64_t ns,
                const float* qx, const float* qy, const float* qz, const float* frames, const float* rnd,
                const int32_t* rank, const int* dens, int64_t nq, const float* tables, float rr, float* desc,
                float* rf, int* err) {
-  hipStream_t st = ctx->stream;
-  // a neighbourhood can only outgrow the first pass when the surface has more points than that
-  const bool second_pass = ns > kScCapSmall;
-  int32_t* over = second_pass ? ctx->buf("sc_over").as<int32_t>((size_t)nq) : nullptr;
-  k_shape_context<kScCapSmall, USC><<<(unsigned)std::min<int64_t>(nq, 1 << 20), kScChunk, kLdsSmall, st>>>(
-      g, snx, sny, snz, qx, qy, qz, frames, rnd, rank, dens, nq, nullptr, nullptr, over, tables, rr, desc, rf, err);
-  if (second_pass) {
-    PFX_HIP(hipFuncSetAttribute((const void*)k_shape_context<kScCap, USC>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLarge));
-    // longer lists: the count stays on the device
-    k_shape_context<kScCap, USC><<<(unsigned)std::min<int64_t>(nq, 256), kScChunk, kLdsLarge, st>>>(
-        g, snx, sny, snz, qx, qy, qz, frames, rnd, rank, dens, nq, over, err + 2, nullptr, tables, rr, desc, rf, err);
-  }
+  two_pass(ctx, ns, nq, "sc_over", err,
+           [&](auto cap, unsigned blocks, size_t lds, const int32_t* list, const int* n_list, int32_t* over) {
+             two_pass_launch(k_shape_context<cap(), USC>, blocks, lds, ctx->stream, g, snx, sny, snz, qx, qy, qz,
+                             frames, rnd, rank, dens, nq, list, n_list, over, tables, rr, desc, rf, err);
+           });
   check_launch("k_shape_context");
 }
 
 }  // namespace
 
-int sc_cap_small() { return kScCapSmall; }
+int sc_cap_small() { return kTwoPassCapSmall; }
 
 void rng_uniform01(uint32_t seed, int64_t skip, int64_t n, float* out) {
   std::mt19937 eng(seed);  // init_genrand(seed)
@@ -465,11 +406,7 @@ void sc_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, con
   if (nq == 0) return;
   hipStream_t st = ctx->stream;
   const bool usc = frames != nullptr;
-  DevBuf& eb = ctx->buf("sc_err");
-  const bool fresh = !eb.ptr;
-  int* err = eb.as<int>(kErrWords);
-  if (fresh) PFX_HIP(hipMemsetAsync(err, 0, 2 * sizeof(int), st));          // the sticky words start clear
-  PFX_HIP(hipMemsetAsync(err + 2, 0, (kErrWords - 2) * sizeof(int), st));  // the per-call words
+  int* err = report_words(ctx, kRepSc);
   if (ns == 0) {
     const unsigned bl = (unsigned)std::min<int64_t>(nq, 1 << 16);
     if (usc) k_sc_empty<true><<<bl, kScChunk, 0, st>>>(qx, qy, qz, frames, nq, desc, rf);
@@ -522,76 +459,41 @@ void sc_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, con
     if (usc) sc_launch<true>(ctx, g, snx, sny, snz, ns, qx, qy, qz, frames, rnd, rank, dens, nq, tables, rr, desc, rf, err);
     else sc_launch<false>(ctx, g, snx, sny, snz, ns, qx, qy, qz, frames, rnd, rank, dens, nq, tables, rr, desc, rf, err);
   }
-  // statistics and the error words land in pinned memory in stream order; no host synchronisation
-  PFX_HIP(hipMemcpyAsync(sc_rb(ctx)->sc, err, sizeof(int) * kErrWords, hipMemcpyDeviceToHost, st));
-  ctx->sc_pending = true;
+  report_post(ctx, kRepSc, err);
 }
 
 void shot_lrf_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, const float* qx,
                   const float* qy, const float* qz, int64_t nq, double r, float* rf) {
   if (nq == 0) return;
   hipStream_t st = ctx->stream;
-  DevBuf& eb = ctx->buf("sc_lrf_err");
-  const bool fresh = !eb.ptr;
-  int* err = eb.as<int>(kLrfWords);
-  if (fresh) PFX_HIP(hipMemsetAsync(err, 0, sizeof(int), st));
-  PFX_HIP(hipMemsetAsync(err + 1, 0, (kLrfWords - 1) * sizeof(int), st));
+  int* err = report_words(ctx, kRepLrf);
   if (ns == 0) {
-    k_sc_fill<<<(unsigned)ceil_div(nq * 9, 256), 256, 0, st>>>(rf, nq * 9, __builtin_nanf(""));
-    check_launch("k_sc_fill");
+    fill_nan(ctx, rf, nq * 9);
   } else {
     const GridView g = feature_grid(ctx, sx, sy, sz, ns, r);
-    const bool second_pass = ns > kCapSmall;
-    int32_t* over = second_pass ? ctx->buf("sc_lrf_over").as<int32_t>((size_t)nq) : nullptr;
-    const size_t lds_s = 2 * sizeof(uint64_t) * kCapSmall, lds_l = sizeof(uint64_t) * kCap;
     TimeScope ts(ctx, "shot_lrf", true);
-    k_sc_lrf<kCapSmall><<<(unsigned)std::min<int64_t>(nq, 1 << 20), 256, lds_s, st>>>(g, qx, qy, qz, nq, nullptr,
-                                                                                    nullptr, over, r, rf, err);
-    if (second_pass) {
-      PFX_HIP(hipFuncSetAttribute((const void*)k_sc_lrf<kCap>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds_l));
-      k_sc_lrf<kCap><<<(unsigned)std::min<int64_t>(nq, 256), 256, lds_l, st>>>(g, qx, qy, qz, nq, over, err + 1,
-                                                                              nullptr, r, rf, err);
-    }
+    // (no records behind the keys: the first pass holds its keys and their sort scratch, the second its keys)
+    two_pass(ctx, ns, nq, "sc_lrf_over", err,
+             [&](auto cap, unsigned blocks, size_t lds, const int32_t* list, const int* n_list, int32_t* over) {
+               two_pass_launch(k_sc_lrf<cap()>, blocks, lds, st, g, qx, qy, qz, nq, list, n_list, over, r, rf, err);
+             },
+             2 * sizeof(uint64_t) * kTwoPassCapSmall, sizeof(uint64_t) * kTwoPassCap);
     check_launch("k_sc_lrf");
   }
-  PFX_HIP(hipMemcpyAsync(sc_rb(ctx)->lrf, err, sizeof(int) * kLrfWords, hipMemcpyDeviceToHost, st));
-  ctx->lrf_pending = true;
+  report_post(ctx, kRepLrf, err);
 }
 
-// After a synchronisation of ctx's stream: the last sc_dev's statistics, and its and the last
-// shot_lrf_dev's capacity errors, each reported once.
-void sc_resolve(pfx_ctx* ctx) {
-  if (ctx->sc_pending) {
-    ctx->sc_pending = false;
-    const int* h = sc_rb(ctx)->sc;
-    unsigned long long nb;
-    std::memcpy(&nb, h + 4, sizeof(nb));
-    ctx->stats["sc_neighbors"] = (int64_t)nb;
-    ctx->stats["sc_queued"] = h[2];
-    ctx->stats["sc_kmax"] = h[3];
-    ctx->stats["sc_draws"] = h[6];
-    ctx->stats["sc_skipped_close"] = h[7];
-    ctx->stats["sc_support"] = h[8];
-    if (h[0] > 0) {
-      const int cap = h[0];
-      int* err = ctx->buf("sc_err").as<int>(kErrWords);
-      PFX_HIP(hipMemsetAsync(err, 0, 2 * sizeof(int), ctx->stream));  // reported once
-      throw Error(PFX_ERR_CAPACITY, "shape_context: a query has " + std::to_string(cap) + " neighbours (> " +
-                                        std::to_string(kScCap) + " supported)");
-    }
-  }
-  if (ctx->lrf_pending) {
-    ctx->lrf_pending = false;
-    const int* h = sc_rb(ctx)->lrf;
-    if (h[0] > 0) {
-      const int cap = h[0];
-      int* err = ctx->buf("sc_lrf_err").as<int>(kLrfWords);
-      PFX_HIP(hipMemsetAsync(err, 0, sizeof(int), ctx->stream));  // reported once
-      throw Error(PFX_ERR_CAPACITY, "shot_lrf: a query has " + std::to_string(cap) + " neighbours (> " +
-                                        std::to_string(kCap) + " supported)");
-    }
-  }
+void sc_report(pfx_ctx* ctx, const int* h) {
+  ctx->stats["sc_draws"] = h[kWordDraws];
+  ctx->stats["sc_skipped_close"] = h[kWordSkipped];
+  ctx->stats["sc_support"] = h[kWordSupport];
+  two_pass_report(ctx, h, "sc", "shape_context");
+}
+
+void lrf_report(pfx_ctx*, const int* h) {
+  if (h[kWordOver] > 0)
+    throw Error(PFX_ERR_CAPACITY, "shot_lrf: a query has " + std::to_string(h[kWordOver]) + " neighbours (> " +
+                                      std::to_string(kTwoPassCap) + " supported)");
 }
 
 }  // namespace pfx

@@ -432,14 +432,7 @@ void shot_color_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float*
     ctx->stats["shot_color_lut_clamped"] = h_cl;
     return;
   }
-  const bool grid_ready = ctx->prep_x == sx && ctx->prep_n == ns && ctx->prep_r == r;
-  if (grid_ready) fpfh_validate_grid(ctx);
-  ctx->prep_x = nullptr;  // one-shot
-  ctx->prep_n = -1;
-  ctx->prep_qx = nullptr;
-  ctx->prep_nq = -1;
-  if (!grid_ready) build_grid(ctx, ctx->grid_b, sx, sy, sz, ns, r);
-  GridView g = view(ctx->grid_b);
+  GridView g = feature_grid(ctx, sx, sy, sz, ns, r);
   {
     TimeScope ts(ctx, "shot_color", true);
     int32_t* over = ctx->buf("shot_over").as<int32_t>(nq);

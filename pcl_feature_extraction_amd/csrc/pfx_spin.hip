@@ -2,8 +2,7 @@
 // on gfx950.  DESIGN.md "Spin images" and "Spin images: the contract".
 //
 // One 256-thread workgroup per query:
-//   1. radius neighbours in FLANN order, the keys in LDS (pfx_neighbors.h: the bucketed sort for
-//      k <= kSpinCapSmall, longer lists queued for a second pass with kSpinCap keys);
+//   1. radius neighbours in FLANN order, the keys in LDS (pfx_two_pass.h: the two passes);
 //   2. per chunk of kSpinChunk neighbours every thread turns its neighbour into a record, the
 //      four double weights of the bilinear update, and sets its bit in the chunk's row mask of
 //      its alpha_bin and column mask of its beta_bin (64-bit integer atomics in LDS, order-free);
@@ -18,34 +17,28 @@
 //      DESIGN.md);
 //   4. m.sum() in Eigen 3.2's order (pfx_eigen_redux.h: four lanes hold the four running sums,
 //      one lane combines them), m *= 1 / sum for k > 1, the cast to float.
-// Stream-ordered: errors and statistics go to pinned memory in stream order (spin_resolve).
+// Stream-ordered: errors and statistics go through the deferred reports (spin_report).
 #include <cfloat>
 #include <climits>
 #include <cstring>
 
 #include "pfx_eigen_redux.h"
-#include "pfx_neighbors.h"
+#include "pfx_two_pass.h"
 
 namespace pfx {
 namespace {
 
-constexpr int kSpinCapSmall = 2048;  // keys of the first pass (bucketed sort: 2 x 16 KiB of LDS)
-constexpr int kSpinCap = 16384;      // keys of the second pass (128 KiB: one workgroup per CU)
-constexpr int kSpinChunk = 256;      // neighbours per chunk of records = the block size
+constexpr int kSpinChunk = kTwoPassChunk;
 constexpr int kSpinMaxW = 16;
 constexpr int kSpinMaxS = (kSpinMaxW + 1) * (2 * kSpinMaxW + 1);  // 561
 constexpr int kSpinPasses = (kSpinMaxS + kSpinChunk - 1) / kSpinChunk;  // bins per thread
 constexpr int kSpinWords = kSpinChunk / 64;                       // mask words per chunk
 constexpr int kSpinMaskRows = (kSpinMaxW + 2) + (2 * kSpinMaxW + 2);  // row masks, then column masks
 
-// err words (ints).  Sticky until reported: [0] largest k beyond kSpinCap, [1] / [2] INT_MAX - the
-// first row with too few neighbours / a cosine out of range (0: none).  Per call: [4] queued
-// queries, [5] max k, [6..7] neighbours (u64), [8] rows with too few neighbours, [9] rows with a
-// cosine out of range.
-constexpr int kErrWords = 12;
-struct SpinReadback {
-  int h[kErrWords];
-};
+// The family's own words.  Sticky: INT_MAX - the first row with too few neighbours / with a cosine
+// out of range (0: none).  Per call: the rows with too few neighbours / a cosine out of range.
+constexpr int kWordFewRow = kWordSticky, kWordBadRow = kWordSticky + 1;
+constexpr int kWordFew = kWordOwn, kWordBad = kWordOwn + 1;
 
 // The 16 KiB behind the keys: the bucketed sort's scratch, then (the sort done) the chunk's records
 // and the finished matrix in Eigen's column-major order.
@@ -62,7 +55,7 @@ struct SpinAux {
   double sum, inv;
   int bad;
 };
-static_assert(sizeof(SpinAux) <= sizeof(uint64_t) * kSpinCapSmall, "the records fit the sort scratch");
+static_assert(sizeof(SpinAux) <= kTwoPassAuxBytes, "the records fit the sort scratch");
 
 struct SpinParams {
   double bin_size, support_cos;
@@ -97,31 +90,24 @@ __global__ void __launch_bounds__(kSpinChunk) k_spin(GridView g, const float* __
   const int W = P.W, rows = W + 1, cols = 2 * W + 1, S = rows * cols;
   const double lim = 1.0 + (double)(10.0f * FLT_EPSILON), tiny = (double)(10.0f * FLT_EPSILON);
   const double edge = P.bin_size * W;
-  unsigned long long* nbr = reinterpret_cast<unsigned long long*>(err + 6);
   const int64_t count = list ? (int64_t)*n_list : nq;
   for (int64_t wi = blockIdx.x; wi < count; wi += gridDim.x) {
     const int64_t q = list ? (int64_t)list[wi] : wi;
     const float cx = qx[q], cy = qy[q], cz = qz[q];
     // (a non-finite query has no candidate run: k = 0)
-    const int k = CAP == kSpinCapSmall
-                      ? sorted_neighbors_bucketed(g, cx, cy, cz, P.rr, keys, keys + CAP, CAP, &s_count, SB)
-                      : sorted_neighbors(g, cx, cy, cz, P.rr, keys, CAP, &s_count);
+    const int k = two_pass_neighbors<CAP>(g, cx, cy, cz, P.rr, keys, &s_count, SB);
     if (k > CAP) {
-      if (tid == 0) {
-        if (over) over[atomicAdd(err + 4, 1)] = (int32_t)q;
-        else { atomicMax(err, k); atomicMax(err + 5, k); }
-      }
+      if (tid == 0) over_or_err(k, q, over, err);
       continue;
     }
     if (tid == 0) {
-      atomicAdd(nbr, (unsigned long long)k);
-      atomicMax(err + 5, k);
+      count_neighbors(k, err);
       A.bad = 0;
     }
     if (k < P.min_pts) {  // PCL throws: reported after the call, the row is unspecified
       if (tid == 0) {
-        atomicAdd(err + 8, 1);
-        atomicMax(err + 1, INT_MAX - (int)q);
+        atomicAdd(err + kWordFew, 1);
+        atomicMax(err + kWordFewRow, INT_MAX - (int)q);
       }
       continue;
     }
@@ -260,8 +246,8 @@ __global__ void __launch_bounds__(kSpinChunk) k_spin(GridView g, const float* __
     if (tid == 0) {
       if (sums) sums[q] = k > 1 ? A.sum : 0.0;
       if (A.bad) {
-        atomicAdd(err + 9, 1);
-        atomicMax(err + 2, INT_MAX - (int)q);
+        atomicAdd(err + kWordBad, 1);
+        atomicMax(err + kWordBadRow, INT_MAX - (int)q);
       }
     }
     __syncthreads();  // A is read before the next query's sort scratch overwrites it
@@ -271,14 +257,14 @@ __global__ void __launch_bounds__(kSpinChunk) k_spin(GridView g, const float* __
 // no surface: every neighbourhood is empty
 __global__ void k_spin_empty(int64_t nq, int min_pts, int* __restrict__ err) {
   if (threadIdx.x == 0 && blockIdx.x == 0 && min_pts > 0) {
-    err[8] = (int)(nq < INT_MAX ? nq : INT_MAX);
-    atomicMax(err + 1, INT_MAX);
+    err[kWordFew] = (int)(nq < INT_MAX ? nq : INT_MAX);
+    atomicMax(err + kWordFewRow, INT_MAX);
   }
 }
 
 }  // namespace
 
-int spin_cap_small() { return kSpinCapSmall; }
+int spin_cap_small() { return kTwoPassCapSmall; }
 int spin_chunk() { return kSpinChunk; }
 
 void spin_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx, const float* sny,
@@ -288,11 +274,7 @@ void spin_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, c
   if (nq == 0) return;
   hipStream_t st = ctx->stream;
   const int W = prm.image_width, S = (W + 1) * (2 * W + 1);
-  DevBuf& eb = ctx->buf("spin_err");
-  const bool fresh = !eb.ptr;
-  int* err = eb.as<int>(kErrWords);
-  if (fresh) PFX_HIP(hipMemsetAsync(err, 0, 4 * sizeof(int), st));          // the sticky words start clear
-  PFX_HIP(hipMemsetAsync(err + 4, 0, (kErrWords - 4) * sizeof(int), st));  // the per-call words
+  int* err = report_words(ctx, kRepSpin);
   if (ns == 0) {
     PFX_HIP(hipMemsetAsync(out, 0, sizeof(float) * (size_t)nq * S, st));
     if (raw) PFX_HIP(hipMemsetAsync(raw, 0, sizeof(double) * (size_t)nq * S, st));
@@ -300,66 +282,38 @@ void spin_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, c
     k_spin_empty<<<1, 64, 0, st>>>(nq, prm.min_pts_neighb, err);
     check_launch("k_spin_empty");
   } else {
-    // the surface grid prepared ahead (pfx_fpfh_prepare_dev: coordinates only), else built here
-    const bool grid_ready = ctx->prep_x == sx && ctx->prep_n == ns && ctx->prep_r == r;
-    if (grid_ready) fpfh_validate_grid(ctx);  // (a speculative prepared grid: exact after this)
-    ctx->prep_x = nullptr;  // one-shot
-    ctx->prep_n = -1;
-    ctx->prep_qx = nullptr;
-    ctx->prep_nq = -1;
-    if (!grid_ready) build_grid(ctx, ctx->grid_b, sx, sy, sz, ns, r);
-    const GridView g = view(ctx->grid_b);
+    const GridView g = feature_grid(ctx, sx, sy, sz, ns, r);
     SpinParams P;
     P.bin_size = r / W / std::sqrt(2.0);  // left to right, in double
     P.support_cos = prm.support_angle_cos;
     P.rr = (float)(r * r);
     P.W = W;
     P.min_pts = prm.min_pts_neighb;
-    // a neighbourhood can only outgrow the first pass when the surface has more points than that
-    const bool second_pass = ns > kSpinCapSmall;
-    int32_t* over = second_pass ? ctx->buf("spin_over").as<int32_t>((size_t)nq) : nullptr;
-    const size_t aux = sizeof(uint64_t) * kSpinCapSmall;
-    const size_t lds_s = sizeof(uint64_t) * kSpinCapSmall + aux, lds_l = sizeof(uint64_t) * kSpinCap + aux;
     TimeScope ts(ctx, "spin_image", true);
-    // one workgroup per query, dispatched as CUs free up (without a second pass `over` is null and
-    // never reached: k <= ns <= kSpinCapSmall)
-    k_spin<kSpinCapSmall><<<(unsigned)std::min<int64_t>(nq, 1 << 20), kSpinChunk, lds_s, st>>>(
-        g, snx, sny, snz, qx, qy, qz, ax, ay, az, nq, nullptr, nullptr, over, P, out, raw, sums, err);
-    if (second_pass) {
-      PFX_HIP(hipFuncSetAttribute((const void*)k_spin<kSpinCap>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds_l));
-      // longer lists: the count stays on the device
-      k_spin<kSpinCap><<<(unsigned)std::min<int64_t>(nq, 256), kSpinChunk, lds_l, st>>>(
-          g, snx, sny, snz, qx, qy, qz, ax, ay, az, nq, over, err + 4, nullptr, P, out, raw, sums, err);
-    }
+    two_pass(ctx, ns, nq, "spin_over", err,
+             [&](auto cap, unsigned blocks, size_t lds, const int32_t* list, const int* n_list, int32_t* over) {
+               two_pass_launch(k_spin<cap()>, blocks, lds, st, g, snx, sny, snz, qx, qy, qz, ax, ay, az, nq, list,
+                               n_list, over, P, out, raw, sums, err);
+             });
     check_launch("k_spin");
   }
-  // statistics and the error words land in pinned memory in stream order; no host synchronisation
-  if (!ctx->spin_rb_mem) PFX_HIP(hipHostMalloc(&ctx->spin_rb_mem, sizeof(SpinReadback), hipHostMallocDefault));
-  PFX_HIP(hipMemcpyAsync(ctx->spin_rb_mem, err, sizeof(SpinReadback), hipMemcpyDeviceToHost, st));
-  ctx->spin_pending = true;
+  report_post(ctx, kRepSpin, err);
 }
 
-// After a synchronisation of ctx's stream: the last spin_dev's statistics and its errors
-// (PFX_ERR_CAPACITY; PFX_ERR_INVALID where PCL throws), reported once.
-void spin_resolve(pfx_ctx* ctx) {
-  if (!ctx->spin_pending) return;
-  ctx->spin_pending = false;
-  const int* h = static_cast<const SpinReadback*>(ctx->spin_rb_mem)->h;
+// The last spin_dev's statistics and its errors (PFX_ERR_CAPACITY; PFX_ERR_INVALID where PCL throws).
+void spin_report(pfx_ctx* ctx, const int* h) {
   unsigned long long nb;
-  std::memcpy(&nb, h + 6, sizeof(nb));
+  std::memcpy(&nb, h + kWordNeighbors, sizeof(nb));
   ctx->stats["spin_neighbors"] = (int64_t)nb;
-  ctx->stats["spin_queued"] = h[4];
-  ctx->stats["spin_kmax"] = h[5];
-  ctx->stats["spin_too_few"] = h[8];
-  ctx->stats["spin_bad_cos"] = h[9];
-  if (h[0] > 0 || h[1] > 0 || h[2] > 0) {
-    const int cap = h[0], few = h[1], bad = h[2];
-    int* err = ctx->buf("spin_err").as<int>(kErrWords);
-    PFX_HIP(hipMemsetAsync(err, 0, 4 * sizeof(int), ctx->stream));  // reported once
+  ctx->stats["spin_queued"] = h[kWordQueued];
+  ctx->stats["spin_kmax"] = h[kWordKmax];
+  ctx->stats["spin_too_few"] = h[kWordFew];
+  ctx->stats["spin_bad_cos"] = h[kWordBad];
+  const int cap = h[kWordOver], few = h[kWordFewRow], bad = h[kWordBadRow];
+  if (cap > 0 || few > 0 || bad > 0) {
     if (cap > 0)
       throw Error(PFX_ERR_CAPACITY, "spin_image: a query has " + std::to_string(cap) + " neighbours (> " +
-                                        std::to_string(kSpinCap) + " supported)");
+                                        std::to_string(kTwoPassCap) + " supported)");
     // the first offending row; a row breaks one rule only (too few neighbours stops it)
     if (few >= bad)
       throw Error(PFX_ERR_INVALID, "spin_image: query row " + std::to_string(INT_MAX - few) +
