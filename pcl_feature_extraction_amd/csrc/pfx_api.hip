@@ -71,6 +71,26 @@ void check_ctx(pfx_ctx* ctx) {
   }
 }
 
+// the host form of pfx_normals and pfx_normals_fast: stage, run `impl`, copy the four columns back
+using NormalsImpl = void (*)(pfx_ctx*, const float*, const float*, const float*, int64_t, double, const float*, float*,
+                             float*, float*, float*);
+void normals_host(pfx_ctx* ctx, NormalsImpl impl, const char* what, const float* x, const float* y, const float* z,
+                  int64_t n, double radius, const float viewpoint[3], float* nx, float* ny, float* nz,
+                  float* curvature) {
+  check_ctx(ctx);
+  if (n < 0 || (n && (!x || !y || !z || !nx || !ny || !nz || !curvature)))
+    throw Error(PFX_ERR_INVALID, std::string(what) + ": invalid arguments");
+  const Dev3 d = stage3(ctx, "in_", x, y, z, n);
+  float* o = ctx->buf("out_normals").as<float>(4 * n + 4);
+  const float vp0[3] = {0.f, 0.f, 0.f};
+  impl(ctx, d.x, d.y, d.z, n, radius, viewpoint ? viewpoint : vp0, o, o + n, o + 2 * n, o + 3 * n);
+  rows_out(ctx, nx, o, n, 1);
+  rows_out(ctx, ny, o + n, n, 1);
+  rows_out(ctx, nz, o + 2 * n, n, 1);
+  rows_out(ctx, curvature, o + 3 * n, n, 1);
+  PFX_HIP(hipStreamSynchronize(ctx->stream));
+}
+
 }  // namespace
 
 extern "C" {
@@ -330,22 +350,7 @@ pfx_status pfx_normals_fast_dev(pfx_ctx* ctx, const float* d_x, const float* d_y
 pfx_status pfx_normals_fast(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, double radius,
                             const float viewpoint[3], float* nx, float* ny, float* nz, float* curvature) {
   PFX_API_BEGIN
-  check_ctx(ctx);
-  if (n < 0 || (n && (!x || !y || !z || !nx || !ny || !nz || !curvature)))
-    throw Error(PFX_ERR_INVALID, "normals_fast: invalid arguments");
-  float* dx = stage_in(ctx, "in_x", x, n);
-  float* dy = stage_in(ctx, "in_y", y, n);
-  float* dz = stage_in(ctx, "in_z", z, n);
-  float* o = ctx->buf("out_normals").as<float>(4 * n + 4);
-  const float vp0[3] = {0.f, 0.f, 0.f};
-  pfx::normals_fast_dev(ctx, dx, dy, dz, n, radius, viewpoint ? viewpoint : vp0, o, o + n, o + 2 * n, o + 3 * n);
-  if (n) {
-    PFX_HIP(hipMemcpyAsync(nx, o, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-    PFX_HIP(hipMemcpyAsync(ny, o + n, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-    PFX_HIP(hipMemcpyAsync(nz, o + 2 * n, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-    PFX_HIP(hipMemcpyAsync(curvature, o + 3 * n, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  normals_host(ctx, pfx::normals_fast_dev, "normals_fast", x, y, z, n, radius, viewpoint, nx, ny, nz, curvature);
   PFX_API_END(ctx)
 }
 
@@ -433,22 +438,7 @@ pfx_status pfx_normals_chains_dev(pfx_ctx* ctx, pfx_ctx* lists_ctx, const uint8_
 pfx_status pfx_normals(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, double radius,
                        const float viewpoint[3], float* nx, float* ny, float* nz, float* curvature) {
   PFX_API_BEGIN
-  check_ctx(ctx);
-  if (n < 0 || (n && (!x || !y || !z || !nx || !ny || !nz || !curvature)))
-    throw Error(PFX_ERR_INVALID, "normals: invalid arguments");
-  float* dx = stage_in(ctx, "in_x", x, n);
-  float* dy = stage_in(ctx, "in_y", y, n);
-  float* dz = stage_in(ctx, "in_z", z, n);
-  float* out = ctx->buf("out_normals").as<float>(4 * n + 4);
-  const float vp0[3] = {0.f, 0.f, 0.f};
-  pfx::normals_dev(ctx, dx, dy, dz, n, radius, viewpoint ? viewpoint : vp0, out, out + n, out + 2 * n, out + 3 * n);
-  if (n) {
-    PFX_HIP(hipMemcpyAsync(nx, out, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-    PFX_HIP(hipMemcpyAsync(ny, out + n, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-    PFX_HIP(hipMemcpyAsync(nz, out + 2 * n, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-    PFX_HIP(hipMemcpyAsync(curvature, out + 3 * n, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  normals_host(ctx, pfx::normals_dev, "normals", x, y, z, n, radius, viewpoint, nx, ny, nz, curvature);
   PFX_API_END(ctx)
 }
 
@@ -1297,6 +1287,41 @@ extern "C" pfx_status pfx_cloud_resolution(pfx_ctx* ctx, const float* x, const f
   PFX_API_END(ctx)
 }
 
+namespace {
+// the detectors' "n_out / cap / idx" arguments
+void check_keypoints_out(const int64_t* n_out, int64_t cap, const int32_t* idx, const char* what) {
+  if (!n_out || cap < 0 || (cap && !idx)) throw Error(PFX_ERR_INVALID, std::string(what) + ": invalid output arguments");
+}
+// the late report of a result that the caller's arrays cannot hold (the counts are already stored)
+void check_capacity(bool over, const char* what, int64_t count, const char* unit) {
+  if (over) throw Error(PFX_ERR_CAPACITY, std::string(what) + ": " + std::to_string(count) + " " + unit + " > cap");
+}
+void check_harris(double radius, int32_t non_max) {
+  if (!(radius > 0.0)) throw Error(PFX_ERR_INVALID, "harris3d: radius must be > 0");
+  if (!non_max) throw Error(PFX_ERR_UNSUPPORTED, "harris3d: only non-maximum suppression is on the accelerated path");
+}
+// the host forms' outputs that every Harris variant shares, staged on the device
+struct HarrisOut {
+  int32_t* idx;
+  float *resp, *corners;
+  int32_t* cidx;
+};
+HarrisOut harris_out(pfx_ctx* ctx, int64_t n, const float* response, const float* corners,
+                     const int32_t* corner_idx) {
+  return HarrisOut{ctx->buf("out_h3_idx").as<int32_t>(n + 1),
+                   response ? ctx->buf("out_h3_resp").as<float>(n + 1) : nullptr,
+                   corners ? ctx->buf("out_h3_corners").as<float>(3 * (n + 1)) : nullptr,
+                   corner_idx ? ctx->buf("out_h3_cidx").as<int32_t>(n + 1) : nullptr};
+}
+void harris_back(pfx_ctx* ctx, const HarrisOut& d, int64_t n, int64_t k, int64_t nc, int32_t* idx, float* response,
+                 float* corners, int32_t* corner_idx) {
+  rows_out(ctx, idx, d.idx, k, 1);
+  rows_out(ctx, response, d.resp, n, 1);
+  rows_out(ctx, corners, d.corners, nc, 3);
+  rows_out(ctx, corner_idx, d.cidx, nc, 1);
+}
+}  // namespace
+
 extern "C" pfx_status pfx_iss_keypoints_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z,
                                             int64_t n, double salient_radius, double non_max_radius,
                                             int32_t min_neighbors, double threshold21, double threshold32,
@@ -1305,11 +1330,11 @@ extern "C" pfx_status pfx_iss_keypoints_dev(pfx_ctx* ctx, const float* d_x, cons
   check_ctx(ctx);
   check_points(d_x, d_y, d_z, n, "iss");
   check_iss(salient_radius, non_max_radius, min_neighbors, threshold21, threshold32);
-  if (!n_out || cap < 0 || (cap && !d_idx)) throw Error(PFX_ERR_INVALID, "iss: invalid output arguments");
+  check_keypoints_out(n_out, cap, d_idx, "iss");
   const int64_t k = pfx::iss_keypoints_dev(ctx, d_x, d_y, d_z, n, salient_radius, non_max_radius, min_neighbors,
                                            threshold21, threshold32, d_idx, cap, d_third);
   *n_out = k;
-  if (k > cap) throw Error(PFX_ERR_CAPACITY, "iss: " + std::to_string(k) + " keypoints > cap");
+  check_capacity(k > cap, "iss", k, "keypoints");
   PFX_API_END(ctx)
 }
 
@@ -1321,28 +1346,19 @@ extern "C" pfx_status pfx_iss_keypoints(pfx_ctx* ctx, const float* x, const floa
   check_ctx(ctx);
   check_points(x, y, z, n, "iss");
   check_iss(salient_radius, non_max_radius, min_neighbors, threshold21, threshold32);
-  if (!n_out || cap < 0 || (cap && !idx)) throw Error(PFX_ERR_INVALID, "iss: invalid output arguments");
-  float* dx = stage_in(ctx, "in_x", x, n);
-  float* dy = stage_in(ctx, "in_y", y, n);
-  float* dz = stage_in(ctx, "in_z", z, n);
+  check_keypoints_out(n_out, cap, idx, "iss");
+  const Dev3 d = stage3(ctx, "in_", x, y, z, n);
   int32_t* di = ctx->buf("out_iss_idx").as<int32_t>(n + 1);
   double* dt = third ? ctx->buf("out_iss_third").as<double>(n + 1) : nullptr;
-  const int64_t k = pfx::iss_keypoints_dev(ctx, dx, dy, dz, n, salient_radius, non_max_radius, min_neighbors,
+  const int64_t k = pfx::iss_keypoints_dev(ctx, d.x, d.y, d.z, n, salient_radius, non_max_radius, min_neighbors,
                                            threshold21, threshold32, di, n, dt);
   *n_out = k;
-  if (k > cap) throw Error(PFX_ERR_CAPACITY, "iss: " + std::to_string(k) + " keypoints > cap");
-  if (k) PFX_HIP(hipMemcpyAsync(idx, di, sizeof(int32_t) * k, hipMemcpyDeviceToHost, ctx->stream));
-  if (third && n) PFX_HIP(hipMemcpyAsync(third, dt, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  check_capacity(k > cap, "iss", k, "keypoints");
+  rows_out(ctx, idx, di, k, 1);
+  rows_out(ctx, third, dt, n, 1);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   PFX_API_END(ctx)
 }
-
-namespace {
-void check_harris(double radius, int32_t non_max) {
-  if (!(radius > 0.0)) throw Error(PFX_ERR_INVALID, "harris3d: radius must be > 0");
-  if (!non_max) throw Error(PFX_ERR_UNSUPPORTED, "harris3d: only non-maximum suppression is on the accelerated path");
-}
-}  // namespace
 
 extern "C" pfx_status pfx_harris3d_keypoints_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z,
                                                  int64_t n, double radius, float threshold, int32_t non_max,
@@ -1353,14 +1369,13 @@ extern "C" pfx_status pfx_harris3d_keypoints_dev(pfx_ctx* ctx, const float* d_x,
   check_ctx(ctx);
   check_points(d_x, d_y, d_z, n, "harris3d");
   check_harris(radius, non_max);
-  if (!n_out || cap < 0 || (cap && !d_idx)) throw Error(PFX_ERR_INVALID, "harris3d: invalid output arguments");
+  check_keypoints_out(n_out, cap, d_idx, "harris3d");
   int64_t nc = 0;
   const int64_t k = pfx::harris3d_dev(ctx, d_x, d_y, d_z, n, radius, threshold, refine, d_idx, cap, d_response,
                                       d_corners, &nc, d_corner_idx);
   *n_out = k;
   if (n_corners) *n_corners = nc;
-  if (k > cap || (d_corners && nc > cap))
-    throw Error(PFX_ERR_CAPACITY, "harris3d: " + std::to_string(std::max(k, nc)) + " keypoints/corners > cap");
+  check_capacity(k > cap || (d_corners && nc > cap), "harris3d", std::max(k, nc), "keypoints/corners");
   PFX_API_END(ctx)
 }
 
@@ -1372,25 +1387,16 @@ extern "C" pfx_status pfx_harris3d_keypoints(pfx_ctx* ctx, const float* x, const
   check_ctx(ctx);
   check_points(x, y, z, n, "harris3d");
   check_harris(radius, non_max);
-  if (!n_out || cap < 0 || (cap && !idx)) throw Error(PFX_ERR_INVALID, "harris3d: invalid output arguments");
-  float* dx = stage_in(ctx, "in_x", x, n);
-  float* dy = stage_in(ctx, "in_y", y, n);
-  float* dz = stage_in(ctx, "in_z", z, n);
-  int32_t* di = ctx->buf("out_h3_idx").as<int32_t>(n + 1);
-  float* dr = response ? ctx->buf("out_h3_resp").as<float>(n + 1) : nullptr;
-  float* dc = corners ? ctx->buf("out_h3_corners").as<float>(3 * (n + 1)) : nullptr;
-  int32_t* dci = corner_idx ? ctx->buf("out_h3_cidx").as<int32_t>(n + 1) : nullptr;
+  check_keypoints_out(n_out, cap, idx, "harris3d");
+  const Dev3 d = stage3(ctx, "in_", x, y, z, n);
+  const HarrisOut o = harris_out(ctx, n, response, corners, corner_idx);
   int64_t nc = 0;
-  const int64_t k = pfx::harris3d_dev(ctx, dx, dy, dz, n, radius, threshold, refine, di, n, dr, dc, &nc, dci);
+  const int64_t k = pfx::harris3d_dev(ctx, d.x, d.y, d.z, n, radius, threshold, refine, o.idx, n, o.resp, o.corners,
+                                      &nc, o.cidx);
   *n_out = k;
   if (n_corners) *n_corners = nc;
-  if (k > cap || (corners && nc > cap))
-    throw Error(PFX_ERR_CAPACITY, "harris3d: " + std::to_string(std::max(k, nc)) + " keypoints/corners > cap");
-  if (k) PFX_HIP(hipMemcpyAsync(idx, di, sizeof(int32_t) * k, hipMemcpyDeviceToHost, ctx->stream));
-  if (response && n) PFX_HIP(hipMemcpyAsync(response, dr, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-  if (corners && nc) PFX_HIP(hipMemcpyAsync(corners, dc, sizeof(float) * 3 * nc, hipMemcpyDeviceToHost, ctx->stream));
-  if (corner_idx && nc)
-    PFX_HIP(hipMemcpyAsync(corner_idx, dci, sizeof(int32_t) * nc, hipMemcpyDeviceToHost, ctx->stream));
+  check_capacity(k > cap || (corners && nc > cap), "harris3d", std::max(k, nc), "keypoints/corners");
+  harris_back(ctx, o, n, k, nc, idx, response, corners, corner_idx);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   PFX_API_END(ctx)
 }
@@ -1405,14 +1411,13 @@ extern "C" pfx_status pfx_harris6d_keypoints_dev(pfx_ctx* ctx, const float* d_x,
   check_points(d_x, d_y, d_z, n, "harris6d");
   if (n && !d_rgb) throw Error(PFX_ERR_INVALID, "harris6d: null rgb");
   check_harris(radius, non_max);
-  if (!n_out || cap < 0 || (cap && !d_idx)) throw Error(PFX_ERR_INVALID, "harris6d: invalid output arguments");
+  check_keypoints_out(n_out, cap, d_idx, "harris6d");
   int64_t nc = 0;
   const int64_t k = pfx::harris6d_dev(ctx, d_x, d_y, d_z, d_rgb, n, radius, threshold, refine, d_idx, cap, d_response,
                                       d_corners, &nc, d_grad, d_corner_idx);
   *n_out = k;
   if (n_corners) *n_corners = nc;
-  if (k > cap || (d_corners && nc > cap))
-    throw Error(PFX_ERR_CAPACITY, "harris6d: " + std::to_string(std::max(k, nc)) + " keypoints/corners > cap");
+  check_capacity(k > cap || (d_corners && nc > cap), "harris6d", std::max(k, nc), "keypoints/corners");
   PFX_API_END(ctx)
 }
 
@@ -1426,29 +1431,20 @@ extern "C" pfx_status pfx_harris6d_keypoints(pfx_ctx* ctx, const float* x, const
   check_points(x, y, z, n, "harris6d");
   if (n && !rgb) throw Error(PFX_ERR_INVALID, "harris6d: null rgb");
   check_harris(radius, non_max);
-  if (!n_out || cap < 0 || (cap && !idx)) throw Error(PFX_ERR_INVALID, "harris6d: invalid output arguments");
-  float* dx = stage_in(ctx, "in_x", x, n);
-  float* dy = stage_in(ctx, "in_y", y, n);
-  float* dz = stage_in(ctx, "in_z", z, n);
+  check_keypoints_out(n_out, cap, idx, "harris6d");
+  const Dev3 d = stage3(ctx, "in_", x, y, z, n);
   uint32_t* dc_rgb = ctx->buf("in_rgb").as<uint32_t>(n + 1);
   if (n) PFX_HIP(hipMemcpyAsync(dc_rgb, rgb, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-  int32_t* di = ctx->buf("out_h3_idx").as<int32_t>(n + 1);
-  float* dr = response ? ctx->buf("out_h3_resp").as<float>(n + 1) : nullptr;
-  float* dc = corners ? ctx->buf("out_h3_corners").as<float>(3 * (n + 1)) : nullptr;
+  const HarrisOut o = harris_out(ctx, n, response, corners, corner_idx);
   float* dg = grad ? ctx->buf("out_h6_grad").as<float>(3 * (n + 1)) : nullptr;
-  int32_t* dci = corner_idx ? ctx->buf("out_h3_cidx").as<int32_t>(n + 1) : nullptr;
   int64_t nc = 0;
-  const int64_t k = pfx::harris6d_dev(ctx, dx, dy, dz, dc_rgb, n, radius, threshold, refine, di, n, dr, dc, &nc, dg, dci);
+  const int64_t k = pfx::harris6d_dev(ctx, d.x, d.y, d.z, dc_rgb, n, radius, threshold, refine, o.idx, n, o.resp,
+                                      o.corners, &nc, dg, o.cidx);
   *n_out = k;
   if (n_corners) *n_corners = nc;
-  if (k > cap || (corners && nc > cap))
-    throw Error(PFX_ERR_CAPACITY, "harris6d: " + std::to_string(std::max(k, nc)) + " keypoints/corners > cap");
-  if (k) PFX_HIP(hipMemcpyAsync(idx, di, sizeof(int32_t) * k, hipMemcpyDeviceToHost, ctx->stream));
-  if (response && n) PFX_HIP(hipMemcpyAsync(response, dr, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-  if (corners && nc) PFX_HIP(hipMemcpyAsync(corners, dc, sizeof(float) * 3 * nc, hipMemcpyDeviceToHost, ctx->stream));
-  if (grad && n) PFX_HIP(hipMemcpyAsync(grad, dg, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
-  if (corner_idx && nc)
-    PFX_HIP(hipMemcpyAsync(corner_idx, dci, sizeof(int32_t) * nc, hipMemcpyDeviceToHost, ctx->stream));
+  check_capacity(k > cap || (corners && nc > cap), "harris6d", std::max(k, nc), "keypoints/corners");
+  harris_back(ctx, o, n, k, nc, idx, response, corners, corner_idx);
+  rows_out(ctx, grad, dg, n, 3);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   PFX_API_END(ctx)
 }

@@ -19,6 +19,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "pfx_internal.h"
+#include "pfx_igrad.h"
 #include "pfx_nblist.h"
 #include "pfx_neighbors.h"
 #include "pfx_eigen6.h"
@@ -28,27 +29,17 @@ namespace pfx {
 
 namespace {
 
-// HarrisKeypoint3D::responseHarris (calculateNormalCovar's SSE branch): lane per list, six
-// float chains over the neighbours with a finite normal in list order, / float(count), then
-// intensity = 0.04f + det - 0.04f * trace * trace (0 when trace == 0)
+// HarrisKeypoint3D::responseHarris (calculateNormalCovar's SSE branch): lane per list (LaneList,
+// pfx_nblist.h), six float chains over the neighbours with a finite normal in list order,
+// / float(count), then intensity = 0.04f + det - 0.04f * trace * trace (0 when trace == 0)
 __global__ void __launch_bounds__(256) k_harris_response(GridView g, NbLists L, const float* __restrict__ nx,
                                                          const float* __restrict__ ny, const float* __restrict__ nz,
                                                          float* __restrict__ resp) {
-  __shared__ int32_t s_rt[9 * 256];
-  const int tid = threadIdx.x;
-  const int64_t j = (int64_t)blockIdx.x * 256 + tid;
+  __shared__ int32_t s_rt[kLaneListTable];
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= L.nq) return;  // no barriers below
-  const int32_t p = L.qpos[j];
-  const int k = L.cnt[j];
-  const uint32_t key = L.skeys[p];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    int32_t s, len;
-    block_run(g, key, r, s, len);
-    s_rt[r * 256 + tid] = s;
-  }
-  const uint32_t* lst = L.list + L.off[j];
-  const int lg = L.lg[j];
+  const LaneList ll(g, L, j, s_rt);
+  const int k = ll.k;
   float sxx = 0.f, sxy = 0.f, sxz = 0.f, syy = 0.f, syz = 0.f, szz = 0.f;
   unsigned count = 0;
   constexpr int kB = 8;
@@ -57,9 +48,7 @@ __global__ void __launch_bounds__(256) k_harris_response(GridView g, NbLists L, 
     float a[kB], b[kB], c[kB];
 #pragma unroll
     for (int t = 0; t < kB; ++t) {
-      const int m = m0 + t < last ? m0 + t : last;
-      const uint32_t e = lst[(int64_t)m << lg];
-      const int32_t q = g.perm[s_rt[entry_run(e) * 256 + tid] + (int32_t)entry_off(e)];
+      const int32_t q = ll.idx(g, m0 + t < last ? m0 + t : last);
       a[t] = nx[q];
       b[t] = ny[q];
       c[t] = nz[q];
@@ -92,130 +81,47 @@ __global__ void __launch_bounds__(256) k_harris_response(GridView g, NbLists L, 
     const float det = c0 * c5 * c7 + 2.0f * c1 * c2 * c6 - c2 * c2 * c5 - c1 * c1 * c7 - c6 * c6 * c0;
     v = 0.04f + det - 0.04f * trace * trace;
   }
-  resp[g.perm[p]] = v;
+  resp[g.perm[ll.p]] = v;
 }
 
 // non-maximum suppression over the same lists (order-free): finite response >= threshold and
-// no neighbour with a larger one
+// no neighbour with a larger one.  The list is opened only for the points that pass the threshold.
 __global__ void __launch_bounds__(256) k_harris_nms(GridView g, NbLists L, const float* __restrict__ resp,
                                                     float thr, uint8_t* __restrict__ flag) {
-  __shared__ int32_t s_rt[9 * 256];
-  const int tid = threadIdx.x;
-  const int64_t j = (int64_t)blockIdx.x * 256 + tid;
+  __shared__ int32_t s_rt[kLaneListTable];
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= L.nq) return;
-  const int32_t p = L.qpos[j];
-  const int32_t i = g.perm[p];
+  const int32_t i = g.perm[L.qpos[j]];
   const float v = resp[i];
   if (!isfinite(v) || v < thr) return;
-  const uint32_t key = L.skeys[p];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    int32_t s, len;
-    block_run(g, key, r, s, len);
-    s_rt[r * 256 + tid] = s;
-  }
-  const uint32_t* lst = L.list + L.off[j];
-  const int lg = L.lg[j], k = L.cnt[j];
+  const LaneList ll(g, L, j, s_rt);
+  const int k = ll.k;
   bool is_max = true;
-  for (int m = 0; m < k && is_max; ++m) {
-    const uint32_t e = lst[(int64_t)m << lg];
-    if (v < resp[g.perm[s_rt[entry_run(e) * 256 + tid] + (int32_t)entry_off(e)]]) is_max = false;
-  }
+  for (int m = 0; m < k && is_max; ++m)
+    if (v < resp[ll.idx(g, m)]) is_max = false;
   if (is_max) flag[i] = 1;
 }
 
 // ---- Harris6D (keypoints.h:164-176): IntensityGradientEstimation + responseTomasi ----------
-// IntensityFieldAccessor<PointXYZRGB>: I = float(299 r + 587 g + 114 b) * 0.001f
-__device__ __forceinline__ float rgb_intensity(uint32_t c) {
-  const int r = (int)((c >> 16) & 255u), g = (int)((c >> 8) & 255u), b = (int)(c & 255u);
-  return (float)(299 * r + 587 * g + 114 * b) * 0.001f;
-}
-// static_cast<uint8_t>(float) as x86-64 gcc compiles it (cvttss2si, low byte): the demeaned
-// intensities are far inside int32, where v_cvt_i32_f32 truncates the same way
-__device__ __forceinline__ int u8_trunc(float v) { return ((int32_t)v) & 255; }
-// IntensityFieldAccessor::demean (write I - mean back into r, g, b) followed by operator()
-__device__ __forceinline__ float rgb_demeaned(uint32_t c, float mean) {
-  const float iv = rgb_intensity(c) - mean;
-  const int r = u8_trunc(iv * 3.34448160535f), g = u8_trunc(iv * 1.70357751278f), b = u8_trunc(iv * 8.77192982456f);
-  return (float)(299 * r + 587 * g + 114 * b) * 0.001f;
-}
-
-// IntensityGradientEstimation::computeFeature + computePointIntensityGradient, then
-// HarrisKeypoint6D's normalisation (|g|^2 > 200 -> unit length, else 0): lane per list, two passes over
-// the FLANN-ordered r-neighbours (centroid and mean intensity, then the demeaned 3x3 system)
+// IntensityGradientEstimation::computeFeature + computePointIntensityGradient (igrad_lane with the
+// RGB accessor, pfx_igrad.h), then HarrisKeypoint6D's normalisation (|g|^2 > 200 -> unit length,
+// else 0)
 __global__ void __launch_bounds__(256) k_intensity_gradient(GridView g, NbLists L, const uint32_t* __restrict__ rgb,
                                                             const float* __restrict__ nx, const float* __restrict__ ny,
                                                             const float* __restrict__ nz, float* __restrict__ gx,
                                                             float* __restrict__ gy, float* __restrict__ gz,
                                                             float* __restrict__ grad_out) {
-  __shared__ int32_t s_rt[9 * 256];
-  const int tid = threadIdx.x;
-  const int64_t j = (int64_t)blockIdx.x * 256 + tid;
+  __shared__ int32_t s_rt[kLaneListTable];
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= L.nq) return;  // no barriers below
-  const int32_t p = L.qpos[j];
-  const int k = L.cnt[j];
-  const uint32_t key = L.skeys[p];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    int32_t s, len;
-    block_run(g, key, r, s, len);
-    s_rt[r * 256 + tid] = s;
-  }
-  const uint32_t* lst = L.list + L.off[j];
-  const int lg = L.lg[j];
-  auto nbr = [&](int m) { const uint32_t e = lst[(int64_t)m << lg];
-                          return g.perm[s_rt[entry_run(e) * 256 + tid] + (int32_t)entry_off(e)]; };
-  float cx = 0.f, cy = 0.f, cz = 0.f, mi = 0.f;
-  for (int m = 0; m < k; ++m) {
-    const int32_t q = nbr(m);
-    cx += g.ux[q];
-    cy += g.uy[q];
-    cz += g.uz[q];
-    mi += rgb_intensity(rgb[q]);
-  }
-  const float rk = 1.0f / (float)k;  // centroid /= float(k): Eigen 3.2 reciprocal
-  cx *= rk;
-  cy *= rk;
-  cz *= rk;
-  mi /= (float)k;
-  const int32_t i = g.perm[p];
+  const LaneList ll(g, L, j, s_rt);
+  const int32_t i = g.perm[ll.p];
   float o[3];
-  if (k < 3) {
+  if (!igrad_lane(g, ll, RgbIntensity{rgb}, i, nx, ny, nz, o)) {
     // IntensityGradientEstimation writes NaN; the normalisation's len > 200 test fails on NaN
     // and its else branch zeroes the gradient
     o[0] = o[1] = o[2] = 0.0f;
   } else {
-    float A00 = 0.f, A01 = 0.f, A02 = 0.f, A11 = 0.f, A12 = 0.f, A22 = 0.f, b0 = 0.f, b1 = 0.f, b2 = 0.f;
-    for (int m = 0; m < k; ++m) {
-      const int32_t q = nbr(m);
-      const float px = g.ux[q] - cx, py = g.uy[q] - cy, pz = g.uz[q] - cz;
-      const float iv = rgb_demeaned(rgb[q], mi);
-      A00 += px * px;
-      A01 += px * py;
-      A02 += px * pz;
-      A11 += py * py;
-      A12 += py * pz;
-      A22 += pz * pz;
-      b0 += px * iv;
-      b1 += py * iv;
-      b2 += pz * iv;
-    }
-    const float A[9] = {A00, A01, A02, A01, A11, A12, A02, A12, A22};
-    const float bv[3] = {b0, b1, b2};
-    float xs[3];
-    colpiv_solve3f(A, bv, xs);
-    const float nv[3] = {nx[i], ny[i], nz[i]};
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      // Identity - n n^T.  The empty asm pins each coefficient in a register: otherwise the
-      // compiler folds (0 - p) * x into x * (-p), which is -0 where the reference's x86 code
-      // (IEEE: 0 - (+0) = +0) gets +0 -- the sign of zero gradient components
-      float m0 = (r == 0 ? 1.0f : 0.0f) - nv[r] * nv[0];
-      float m1 = (r == 1 ? 1.0f : 0.0f) - nv[r] * nv[1];
-      float m2 = (r == 2 ? 1.0f : 0.0f) - nv[r] * nv[2];
-      asm volatile("" : "+v"(m0), "+v"(m1), "+v"(m2));
-      o[r] = (m0 * xs[0] + m1 * xs[1]) + m2 * xs[2];
-    }
     float len = (o[0] * o[0] + o[1] * o[1]) + o[2] * o[2];
     if (len > 200.0f) {
       len = (float)(1.0 / sqrt((double)len));
@@ -243,27 +149,15 @@ __global__ void __launch_bounds__(256) k_harris6d_response(GridView g, NbLists L
                                                            const float* __restrict__ ny, const float* __restrict__ nz,
                                                            const float* __restrict__ gx, const float* __restrict__ gy,
                                                            const float* __restrict__ gz, float* __restrict__ resp) {
-  __shared__ int32_t s_rt[9 * 256];
-  const int tid = threadIdx.x;
-  const int64_t j = (int64_t)blockIdx.x * 256 + tid;
+  __shared__ int32_t s_rt[kLaneListTable];
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= L.nq) return;
-  const int32_t p = L.qpos[j];
-  const int k = L.cnt[j];
-  const uint32_t key = L.skeys[p];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    int32_t s, len;
-    block_run(g, key, r, s, len);
-    s_rt[r * 256 + tid] = s;
-  }
-  const uint32_t* lst = L.list + L.off[j];
-  const int lg = L.lg[j];
+  const LaneList ll(g, L, j, s_rt);
   float cv[21];
 #pragma unroll
   for (int e = 0; e < 21; ++e) cv[e] = 0.f;
-  for (int m = 0; m < k; ++m) {
-    const uint32_t en = lst[(int64_t)m << lg];
-    const int32_t q = g.perm[s_rt[entry_run(en) * 256 + tid] + (int32_t)entry_off(en)];
+  for (int m = 0; m < ll.k; ++m) {
+    const int32_t q = ll.idx(g, m);
     const float a = nx[q], ga = gx[q];
     if (!isfinite(a) || !isfinite(ga)) continue;
     const float v[6] = {a, ny[q], nz[q], ga, gy[q], gz[q]};
@@ -276,7 +170,7 @@ __global__ void __launch_bounds__(256) k_harris6d_response(GridView g, NbLists L
         ++e;
       }
   }
-  resp[g.perm[p]] = eigen6f_value3(cv);
+  resp[g.perm[ll.p]] = eigen6f_value3(cv);
 }
 
 // matrices column-major as Eigen's Matrix3f::coeff(k)
@@ -444,18 +338,35 @@ struct NonNeg {
   __device__ bool operator()(int32_t v) const { return v >= 0; }
 };
 
-}  // namespace
-
-namespace {
-
-__global__ void k_fill_f32(float* __restrict__ p, int64_t n, float v) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) p[i] = v;
+// The head both detectors share.  False: nothing to do.
+bool harris_args(const char* tag, int64_t n, double radius, int64_t* n_corners) {
+  PFX_CHECK(n >= 0, std::string(tag) + ": negative point count");
+  PFX_CHECK(radius > 0.0, std::string(tag) + ": radius must be > 0");
+  if (n_corners) *n_corners = 0;
+  return n > 0;
 }
-void fill_f32(pfx_ctx* ctx, float* p, int64_t n, float v) {
-  if (n <= 0) return;
-  k_fill_f32<<<(unsigned)ceil_div(n, 256), 256, 0, ctx->stream>>>(p, n, v);
-  check_launch("k_fill_f32");
+
+struct HarrisBufs {
+  float *nx, *ny, *nz, *resp;
+};
+
+// HarrisKeypoint3D::initCompute / HarrisKeypoint6D::detectKeypoints: NormalEstimation at the
+// keypoint radius, viewpoint 0 (its lists stay in ctx->normals->L for the kernels above), and the
+// response zeroed (points off the lists keep 0)
+HarrisBufs harris_head(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, double radius,
+                       float* resp_out) {
+  HarrisBufs B;
+  B.nx = ctx->buf("h3_nx").as<float>(n);
+  B.ny = ctx->buf("h3_ny").as<float>(n);
+  B.nz = ctx->buf("h3_nz").as<float>(n);
+  float* cv = ctx->buf("h3_cv").as<float>(n);
+  normals_lists_dev(ctx, x, y, z, n, radius, B.nx, B.ny, B.nz, cv);
+  const float vp[3] = {0.f, 0.f, 0.f};
+  normals_chains_dev(ctx, ctx, nullptr, 1, vp, B.nx, B.ny, B.nz, cv);
+  PFX_CHECK(!ctx->normals->L.compact, "harris: the lane-per-list kernels read 32-bit lists");
+  B.resp = resp_out ? resp_out : ctx->buf("h3_resp").as<float>(n);
+  PFX_HIP(hipMemsetAsync(B.resp, 0, sizeof(float) * n, ctx->stream));
+  return B;
 }
 
 // HarrisKeypoint3D/6D::detectKeypoints after the response (resp, caller order): non-maximum
@@ -524,78 +435,55 @@ int64_t harris_finish_dev(pfx_ctx* ctx, int64_t n, double radius, float threshol
 int64_t harris3d_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, double radius,
                      float threshold, int refine, int32_t* out, int64_t cap, float* resp_out, float* corners_out,
                      int64_t* n_corners, int32_t* corner_idx_out) {
-  PFX_CHECK(n >= 0, "harris3d: negative point count");
-  PFX_CHECK(radius > 0.0, "harris3d: radius must be > 0");
-  if (n_corners) *n_corners = 0;
-  if (n == 0) return 0;
-  hipStream_t st = ctx->stream;
+  if (!harris_args("harris3d", n, radius, n_corners)) return 0;
   TimeScope total(ctx, "harris3d", true);
-  // HarrisKeypoint3D::initCompute: NormalEstimation at the keypoint radius, viewpoint 0
-  float* nx = ctx->buf("h3_nx").as<float>(n);
-  float* ny = ctx->buf("h3_ny").as<float>(n);
-  float* nz = ctx->buf("h3_nz").as<float>(n);
-  float* cv = ctx->buf("h3_cv").as<float>(n);
-  normals_lists_dev(ctx, x, y, z, n, radius, nx, ny, nz, cv);
-  const float vp[3] = {0.f, 0.f, 0.f};
-  normals_chains_dev(ctx, ctx, nullptr, 1, vp, nx, ny, nz, cv);
+  const HarrisBufs B = harris_head(ctx, x, y, z, n, radius, resp_out);
   const NbLists& L = ctx->normals->L;
-  const Grid& G = ctx->grid_a;
-  float* resp = resp_out ? resp_out : ctx->buf("h3_resp").as<float>(n);
-  PFX_HIP(hipMemsetAsync(resp, 0, sizeof(float) * n, st));
   if (L.nq > 0) {
     TimeScope ts(ctx, "harris3d_response");
     const unsigned nb = (unsigned)ceil_div(L.nq, 256);
-    k_harris_response<<<nb, 256, 0, st>>>(view(G), L, nx, ny, nz, resp);
+    k_harris_response<<<nb, 256, 0, ctx->stream>>>(view(ctx->grid_a), L, B.nx, B.ny, B.nz, B.resp);
     check_launch("k_harris_response");
   }
-  return harris_finish_dev(ctx, n, radius, threshold, refine, nx, ny, nz, resp, out, cap, corners_out, n_corners,
-                           "harris3d", corner_idx_out);
+  return harris_finish_dev(ctx, n, radius, threshold, refine, B.nx, B.ny, B.nz, B.resp, out, cap, corners_out,
+                           n_corners, "harris3d", corner_idx_out);
 }
 
 int64_t harris6d_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, const uint32_t* rgb, int64_t n,
                      double radius, float threshold, int refine, int32_t* out, int64_t cap, float* resp_out,
                      float* corners_out, int64_t* n_corners, float* grad_out, int32_t* corner_idx_out) {
-  PFX_CHECK(n >= 0, "harris6d: negative point count");
-  PFX_CHECK(radius > 0.0, "harris6d: radius must be > 0");
-  if (n_corners) *n_corners = 0;
-  if (n == 0) return 0;
+  if (!harris_args("harris6d", n, radius, n_corners)) return 0;
   hipStream_t st = ctx->stream;
   TimeScope total(ctx, "harris6d", true);
-  // HarrisKeypoint6D::detectKeypoints: NormalEstimation at the keypoint radius, viewpoint 0
-  float* nx = ctx->buf("h3_nx").as<float>(n);
-  float* ny = ctx->buf("h3_ny").as<float>(n);
-  float* nz = ctx->buf("h3_nz").as<float>(n);
-  float* cv = ctx->buf("h3_cv").as<float>(n);
-  normals_lists_dev(ctx, x, y, z, n, radius, nx, ny, nz, cv);
-  const float vp[3] = {0.f, 0.f, 0.f};
-  normals_chains_dev(ctx, ctx, nullptr, 1, vp, nx, ny, nz, cv);
+  const HarrisBufs B = harris_head(ctx, x, y, z, n, radius, resp_out);
   const NbLists& L = ctx->normals->L;
-  const Grid& G = ctx->grid_a;
   float* gx = ctx->buf("h6_gx").as<float>(n);
   float* gy = ctx->buf("h6_gy").as<float>(n);
   float* gz = ctx->buf("h6_gz").as<float>(n);
-  float* resp = resp_out ? resp_out : ctx->buf("h3_resp").as<float>(n);
   // points off the lists (non-finite) keep a NaN gradient and a zero response
-  fill_f32(ctx, gx, n, __builtin_nanf(""));
-  fill_f32(ctx, gy, n, __builtin_nanf(""));
-  fill_f32(ctx, gz, n, __builtin_nanf(""));
-  if (grad_out) fill_f32(ctx, grad_out, 3 * n, __builtin_nanf(""));
-  PFX_HIP(hipMemsetAsync(resp, 0, sizeof(float) * n, st));
+  auto fill_nan = [&](float* p, int64_t m) {
+    k_fill<<<(unsigned)ceil_div(m, 256), 256, 0, st>>>(p, m, __builtin_nanf(""));
+    check_launch("k_fill");
+  };
+  fill_nan(gx, n);
+  fill_nan(gy, n);
+  fill_nan(gz, n);
+  if (grad_out) fill_nan(grad_out, 3 * n);
   if (L.nq > 0) {
     const unsigned nb = (unsigned)ceil_div(L.nq, 256);
     {
       TimeScope ts(ctx, "harris6d_gradient");
-      k_intensity_gradient<<<nb, 256, 0, st>>>(view(G), L, rgb, nx, ny, nz, gx, gy, gz, grad_out);
+      k_intensity_gradient<<<nb, 256, 0, st>>>(view(ctx->grid_a), L, rgb, B.nx, B.ny, B.nz, gx, gy, gz, grad_out);
       check_launch("k_intensity_gradient");
     }
     {
       TimeScope ts(ctx, "harris6d_response");
-      k_harris6d_response<<<nb, 256, 0, st>>>(view(G), L, nx, ny, nz, gx, gy, gz, resp);
+      k_harris6d_response<<<nb, 256, 0, st>>>(view(ctx->grid_a), L, B.nx, B.ny, B.nz, gx, gy, gz, B.resp);
       check_launch("k_harris6d_response");
     }
   }
-  return harris_finish_dev(ctx, n, radius, threshold, refine, nx, ny, nz, resp, out, cap, corners_out, n_corners,
-                           "harris6d", corner_idx_out);
+  return harris_finish_dev(ctx, n, radius, threshold, refine, B.nx, B.ny, B.nz, B.resp, out, cap, corners_out,
+                           n_corners, "harris6d", corner_idx_out);
 }
 
 }  // namespace pfx

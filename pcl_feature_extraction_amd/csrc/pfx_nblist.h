@@ -15,6 +15,7 @@
 // consumer that gives consecutive queries to consecutive lanes reads whole cache lines per load.
 #pragma once
 #include "pfx_internal.h"
+#include "pfx_neighbors.h"
 
 namespace pfx {
 
@@ -60,6 +61,48 @@ struct NbLists {
 };
 
 __device__ __forceinline__ int64_t nq_of(const NbLists& L) { return L.nq_dev ? *L.nq_dev : L.nq; }
+
+// The lane-per-list reader: thread `tid` of a 256-thread workgroup walks list j.
+// For lists of 32-bit entries only, i.e. built without `compact` -- it skips list_entry's width
+// test; the host checks !L.compact where such a kernel is launched.
+// The start of each of the nine runs of the query's block sits in the thread's column of a table
+// in LDS, s_rt[r * kLaneListLanes + tid] (consecutive lanes, consecutive banks: conflict-free).
+// Only the calling thread touches its column, so a list may be opened after an early return or
+// inside a branch, and as late as the kernel likes; no barrier is needed around it.
+// (the kernels that open a LaneList are launched with kLaneListLanes = 256 threads per workgroup and
+// compute j = blockIdx.x * 256 + threadIdx.x: the launches must match this constant)
+constexpr int kLaneListLanes = 256;
+constexpr int kLaneListTable = 9 * kLaneListLanes;  // the kernel's `__shared__ int32_t s_rt[kLaneListTable]`
+
+struct LaneList {
+  int32_t p;            // the query's sorted position
+  int k;                // neighbours
+  const uint32_t* lst;  // entry m at lst[m << lg]
+  int lg;
+  const int32_t* s_rt;  // the run table, this thread's column at + tid
+  int tid;
+
+  __device__ __forceinline__ LaneList(const GridView& g, const NbLists& L, int64_t j, int32_t* table)
+      : p(L.qpos[j]), s_rt(table), tid(threadIdx.x) {
+    const uint32_t key = L.skeys[p];
+#pragma unroll
+    for (int r = 0; r < 9; ++r) {
+      int32_t s, len;
+      block_run(g, key, r, s, len);
+      table[r * kLaneListLanes + tid] = s;
+    }
+    lst = L.list + L.off[j];
+    lg = L.lg[j];
+    k = L.cnt[j];
+  }
+  __device__ __forceinline__ uint32_t entry(int m) const { return lst[(int64_t)m << lg]; }
+  // neighbour m's sorted position (an index of g.sp and g.perm) and its caller index
+  __device__ __forceinline__ int32_t pos(int m) const {
+    const uint32_t e = entry(m);
+    return s_rt[entry_run(e) * kLaneListLanes + tid] + (int32_t)entry_off(e);
+  }
+  __device__ __forceinline__ int32_t idx(const GridView& g, int m) const { return g.perm[pos(m)]; }
+};
 
 // lists longer than this are handled by per-query kernels downstream (normals: k_normals_long)
 constexpr int kLongList = 1024;

@@ -4,9 +4,8 @@
 // DESIGN.md "Intensity gradient and RIFT" and "RIFT: the contract".
 //
 // Intensity gradient, two shapes of one arithmetic (the same bits for the same query):
-//   k_igrad_lists  the whole cloud: the normal estimation's FLANN-ordered lists, lane per list, the
-//                  two-pass loop of Harris6D's k_intensity_gradient (pfx_harris.hip) with the float
-//                  accessor I(p) = si[p], demean = I - mean, and no normalisation;
+//   k_igrad_lists  the whole cloud: the normal estimation's FLANN-ordered lists, lane per list,
+//                  igrad_lane (pfx_igrad.h) with the float accessor I(p) = si[p], demean = I - mean;
 //   k_igrad_query  arbitrary queries: one 256-thread workgroup per query, the keys sorted in LDS
 //                  (pfx_neighbors.h), the neighbours' (x, y, z, I) staged in LDS a chunk at a time,
 //                  and one lane per accumulator: four sequential chains in the first pass (centroid,
@@ -28,9 +27,8 @@
 
 #include <string>
 
-#include "pfx_eigen6.h"
 #include "pfx_eigen_redux.h"
-#include "pfx_nblist.h"
+#include "pfx_igrad.h"
 #include "pfx_two_pass.h"
 
 namespace pfx {
@@ -40,30 +38,12 @@ constexpr int kRiftChunk = kTwoPassChunk;
 constexpr int kRiftMaxBins = 16;     // per axis
 constexpr int kNoCol = 31;           // a record's unused column slot (no bin has this column)
 
-// x = colPivHouseholderQr(A).solve(b), gradient = (Identity - n n^T) x
-__device__ __forceinline__ void igrad_finish(const float s[9], const float nv[3], float o[3]) {
-  const float A[9] = {s[0], s[1], s[2], s[1], s[3], s[4], s[2], s[4], s[5]};
-  const float bv[3] = {s[6], s[7], s[8]};
-  float xs[3];
-  colpiv_solve3f(A, bv, xs);
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    // The empty asm pins each coefficient in a register: otherwise the compiler folds
-    // (0 - p) * x into x * (-p), which is -0 where x86 code (IEEE: 0 - (+0) = +0) gets +0
-    float m0 = (r == 0 ? 1.0f : 0.0f) - nv[r] * nv[0];
-    float m1 = (r == 1 ? 1.0f : 0.0f) - nv[r] * nv[1];
-    float m2 = (r == 2 ? 1.0f : 0.0f) - nv[r] * nv[2];
-    asm volatile("" : "+v"(m0), "+v"(m1), "+v"(m2));
-    o[r] = canon_nan((m0 * xs[0] + m1 * xs[1]) + m2 * xs[2]);
-  }
-}
-
-// the whole cloud: lane per list (the rows of points off the lists were filled with NaN)
+// the whole cloud: lane per list (LaneList; the rows of points off the lists were filled with NaN)
 __global__ void __launch_bounds__(256) k_igrad_lists(GridView g, NbLists L, const float* __restrict__ si,
                                                      const float* __restrict__ nx, const float* __restrict__ ny,
                                                      const float* __restrict__ nz, float* __restrict__ out,
                                                      int* __restrict__ err) {
-  __shared__ int32_t s_rt[9 * 256];
+  __shared__ int32_t s_rt[kLaneListTable];
   __shared__ unsigned long long s_sum;
   __shared__ int s_max;
   const int tid = threadIdx.x;
@@ -76,62 +56,14 @@ __global__ void __launch_bounds__(256) k_igrad_lists(GridView g, NbLists L, cons
   __syncthreads();
   int k = 0;
   if (on) {
-    const int32_t p = L.qpos[j];
-    k = L.cnt[j];
-    const uint32_t key = L.skeys[p];
-#pragma unroll
-    for (int r = 0; r < 9; ++r) {
-      int32_t s, len;
-      block_run(g, key, r, s, len);
-      s_rt[r * 256 + tid] = s;
-    }
-    const uint32_t* lst = L.list + L.off[j];
-    const int lg = L.lg[j];
-    auto nbr = [&](int m) { const uint32_t e = lst[(int64_t)m << lg];
-                            return g.perm[s_rt[entry_run(e) * 256 + tid] + (int32_t)entry_off(e)]; };
-    float cx = 0.f, cy = 0.f, cz = 0.f, mi = 0.f;
-    for (int m = 0; m < k; ++m) {
-      const int32_t q = nbr(m);
-      cx += g.ux[q];
-      cy += g.uy[q];
-      cz += g.uz[q];
-      mi += si[q];
-    }
-    const float rk = 1.0f / (float)k;  // centroid /= float(k): Eigen 3.2 reciprocal
-    cx *= rk;
-    cy *= rk;
-    cz *= rk;
-    mi /= (float)k;
-    const int32_t i = g.perm[p];
+    const LaneList ll(g, L, j, s_rt);
+    k = ll.k;
+    const int32_t i = g.perm[ll.p];
     float o[3];
-    if (k < 3) {
-      o[0] = o[1] = o[2] = __uint_as_float(0x7fc00000u);
-    } else {
-      float s[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // A00 A01 A02 A11 A12 A22 b0 b1 b2
-      for (int m = 0; m < k; ++m) {
-        const int32_t q = nbr(m);
-        const float raw = si[q];
-        // a neighbour whose intensity is not finite is skipped: an exact +0 term instead of a branch
-        // (a sum that starts at +0 is never -0, so adding +0 leaves its bits)
-        const bool in = isfinite(raw);
-        const float px = g.ux[q] - cx, py = g.uy[q] - cy, pz = g.uz[q] - cz;
-        const float iv = raw - mi;
-        s[0] += in ? px * px : 0.f;
-        s[1] += in ? px * py : 0.f;
-        s[2] += in ? px * pz : 0.f;
-        s[3] += in ? py * py : 0.f;
-        s[4] += in ? py * pz : 0.f;
-        s[5] += in ? pz * pz : 0.f;
-        s[6] += in ? px * iv : 0.f;
-        s[7] += in ? py * iv : 0.f;
-        s[8] += in ? pz * iv : 0.f;
-      }
-      const float nv[3] = {nx[i], ny[i], nz[i]};
-      igrad_finish(s, nv, o);
-    }
-    out[3 * (int64_t)i] = o[0];
-    out[3 * (int64_t)i + 1] = o[1];
-    out[3 * (int64_t)i + 2] = o[2];
+    if (!igrad_lane(g, ll, FloatIntensity{si}, i, nx, ny, nz, o)) o[0] = o[1] = o[2] = __uint_as_float(0x7fc00000u);
+    out[3 * (int64_t)i] = canon_nan(o[0]);
+    out[3 * (int64_t)i + 1] = canon_nan(o[1]);
+    out[3 * (int64_t)i + 2] = canon_nan(o[2]);
   }
   // statistics: the waves' sums meet in LDS, one pair of global atomics per block (same-address
   // atomics serialise at the L2)
@@ -238,9 +170,9 @@ __global__ void __launch_bounds__(kRiftChunk) k_igrad_query(GridView g, const fl
       for (int e = 0; e < 9; ++e) s[e] = A.acc[4 + e];
       const float nv[3] = {qnx[q], qny[q], qnz[q]};
       igrad_finish(s, nv, o);
-      out[3 * q] = o[0];
-      out[3 * q + 1] = o[1];
-      out[3 * q + 2] = o[2];
+      out[3 * q] = canon_nan(o[0]);
+      out[3 * q + 1] = canon_nan(o[1]);
+      out[3 * q + 2] = canon_nan(o[2]);
     }
     __syncthreads();  // A is read before the next query's sort scratch overwrites it
   }
@@ -379,6 +311,7 @@ void igrad_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, 
     const NbLists& L = ctx->normals->L;
     int* err = report_words(ctx, kRepIgrad);
     fill_nan(ctx, out, 3 * ns);  // points off the lists (non-finite) keep a NaN row
+    PFX_CHECK(!L.compact, "intensity_gradient: the lane-per-list kernel reads 32-bit lists");
     if (L.nq > 0) {
       TimeScope ts(ctx, "intensity_gradient_cloud", true);
       k_igrad_lists<<<(unsigned)ceil_div(L.nq, 256), 256, 0, st>>>(view(ctx->grid_a), L, si, qnx, qny, qnz, out, err);
