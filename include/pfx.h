@@ -32,6 +32,8 @@
  *                          Tools::computeGradient, tools.h:40-54)
  *   pfx_rift*           <- RIFTEstimation<PointXYZI,IntensityGradient,Histogram<32>>::compute
  *                          (evaluation.cpp:716-765)
+ *   pfx_intensity_spin* <- IntensitySpinEstimation<PointXYZI,Histogram<20>>::compute
+ *                          (evaluation.cpp:466-514)
  *   pfx_shape_context*  <- ShapeContext3DEstimation<PointXYZRGB,Normal,ShapeContext1980>::compute
  *                          (features.h:175-196, evaluation.cpp:319-345)
  *   pfx_usc*            <- UniqueShapeContext<PointXYZRGB,ShapeContext1980>::compute
@@ -497,6 +499,43 @@ pfx_status pfx_rift_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, cons
                         const float* d_sgx, const float* d_sgy, const float* d_sgz, int64_t n_surface,
                         const float* d_cx, const float* d_cy, const float* d_cz, int64_t nq, double radius,
                         int32_t nr_distance_bins, int32_t nr_gradient_bins, float* d_out);
+
+/* ---- intensity spin images: IntensitySpinEstimation<PointXYZI, Histogram<20>>
+ *      (evaluation.cpp:466-514) ---------------------------------------------------------------- */
+/* out: nq x D I floats, D = nr_distance_bins and I = nr_intensity_bins, each in [1, 16];
+ * out[distance_bin I + intensity_bin], PCL's copy order.  (cx, cy, cz)[i] is the centre of row i; si
+ * are the surface's intensities (as for pfx_intensity_gradient).  No normals are read.  Over the
+ * radius neighbours of a centre in FLANN order, all in float32 without FMA: the neighbourhood's
+ * intensity range [min, max] (NaN intensities ignored); per neighbour d = D sqrt(d^2) / (radius +
+ * FLT_EPSILON) and i = I (I_n - min) / ((max - min) + FLT_EPSILON); with sigma > 0 every bin
+ * (dj, ii) of the window floor(d - 3 sigma) .. ceil(d + 3 sigma), floor(i - 3 sigma) .. ceil(i +
+ * 3 sigma), clamped to the image, receives pfx_expf(-(d - dj)^2 c - (i - ii)^2 c), c = 1 / (2 sigma
+ * sigma), a float addition per bin in neighbour order.  pfx_expf (csrc/pfx_expf.h) is the contract's
+ * exponential, the same bits on host and device, faithfully rounded; it is not the C library's.
+ * DESIGN.md "Intensity spin: the contract" states every operation; the CPU restatement of that text
+ * is the truth the kernel is tested against (parity with PCL itself is unpinned).  No normalisation
+ * (PCL has none).  A neighbour whose i is not finite (a NaN intensity; a range that overflows)
+ * contributes nothing, so a ball whose intensities are all NaN gives a row of zeros.
+ * Deliberate deviation, sigma == 0: the neighbour adds 1 to the bin ((int)d, (int)i); PCL writes out
+ * of bounds when (int)i == I (the brightest neighbour of almost every ball) or (int)d == D; here
+ * such a neighbour, and one whose i is not finite, is dropped.
+ * No neighbour at all (a non-finite centre included): a NaN row, as PCL.  Every NaN is written as
+ * 0x7fc00000.  Null pointers, negative sizes, radius <= 0 or NaN, D or I outside [1, 16], sigma
+ * negative, NaN or above 2^20: PFX_ERR_INVALID before any launch.  More than 16384 neighbours:
+ * PFX_ERR_CAPACITY.  Statistics: "ispin_neighbors" (sum of k), "ispin_kmax", "ispin_queued" (rows
+ * with more than "ispin_cap_small" neighbours, which take the second pass); "ispin_cap_small",
+ * "ispin_tile_words" and "ispin_tile" (the neighbours whose weights are formed at once: min(256,
+ * ispin_tile_words / (D I | 1)), given for D I = 20) can be read from a new ctx. */
+pfx_status pfx_intensity_spin(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* si,
+                              int64_t n_surface, const float* cx, const float* cy, const float* cz, int64_t nq,
+                              double radius, int32_t nr_distance_bins, int32_t nr_intensity_bins, float sigma,
+                              float* out);
+/* Device pointers, stream-ordered on the ctx stream, no host synchronisation; late errors and
+ * statistics as pfx_spin_image_dev. */
+pfx_status pfx_intensity_spin_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                                  const float* d_si, int64_t n_surface, const float* d_cx, const float* d_cy,
+                                  const float* d_cz, int64_t nq, double radius, int32_t nr_distance_bins,
+                                  int32_t nr_intensity_bins, float sigma, float* d_out);
 
 /* ---- 3D shape contexts: ShapeContext3DEstimation<PointXYZRGB, Normal, ShapeContext1980>
  * (evaluation.cpp:319-345) and UniqueShapeContext<PointXYZRGB, ShapeContext1980> (:346-371) ---- */

@@ -215,7 +215,7 @@ struct PrincipalCurvatures {
 static_assert(sizeof(PrincipalCurvatures) == 20, "pcl::PrincipalCurvatures is 20 bytes");
 struct FPFHSignature33 { float histogram[33]; };
 struct PFHSignature125 { float histogram[125]; };
-// pcl::Histogram<N> (spin images, RIFT, and later intensity spin): N floats, nothing else
+// pcl::Histogram<N> (spin images, RIFT, intensity spin images): N floats, nothing else
 template <int N>
 struct Histogram {
   float histogram[N];
@@ -830,6 +830,63 @@ class RIFTEstimation : public Feature<PointInT, PointOutT> {
   }
   PointCloudGradientConstPtr gradient_;
   int nr_distance_bins_ = 4, nr_gradient_bins_ = 4;
+};
+
+// ---- intensity spin images (evaluation.cpp:466-514) --------------------------------------------
+// IntensitySpinEstimation<PointXYZI, Histogram<20>> with PCL 1.7's indexing, which is RIFT's:
+// `tree_->radiusSearch ((*indices_)[idx], ...)` searches at surface_[idx], so row i describes
+// surface_[i], not input point i (the input cloud only sets the number of rows): those surface
+// points are the centres passed to pfx_intensity_spin.  A caller who wants the descriptor at the
+// keypoints calls pfx_intensity_spin with them.  No normals are read.  A row without neighbours is
+// NaN, as PCL's.  sigma == 0 drops the neighbours PCL would write out of bounds (pfx.h).
+template <typename PointInT, typename PointOutT>
+class IntensitySpinEstimation : public Feature<PointInT, PointOutT> {
+ public:
+  typedef std::shared_ptr<IntensitySpinEstimation<PointInT, PointOutT> > Ptr;
+  IntensitySpinEstimation() { this->name_ = "IntensitySpinEstimation"; }
+  void setNrDistanceBins(size_t nr_distance_bins) { nr_distance_bins_ = (int)nr_distance_bins; }
+  int getNrDistanceBins() { return nr_distance_bins_; }
+  void setNrIntensityBins(size_t nr_intensity_bins) { nr_intensity_bins_ = (int)nr_intensity_bins; }
+  int getNrIntensityBins() { return nr_intensity_bins_; }
+  void setSmoothingBandwidth(float sigma) { sigma_ = sigma; }
+  float getSmoothingBandwidth() { return sigma_; }
+
+ protected:
+  void computeFeature(PointCloud<PointOutT>& out) override {
+    const PointCloud<PointInT>& surf = this->surface();
+    const size_t nq = this->input_->size(), ns = surf.size();
+    const int D = nr_distance_bins_, I = nr_intensity_bins_;
+    if (nq > ns) {  // row i reads surface_[i]
+      PCL_ERROR("[pcl::IntensitySpinEstimation::compute] input index %zu is beyond the search surface (%zu points)\n",
+                ns, ns);
+      return;
+    }
+    if (D < 1 || D > 16 || I < 1 || I > 16 || (size_t)(D * I) != sizeof(PointOutT) / sizeof(float)) {
+      PCL_ERROR("[pcl::IntensitySpinEstimation::compute] nr_distance_bins * nr_intensity_bins = %d does not match "
+                "the output histogram (each in [1, 16])\n", D * I);
+      return;
+    }
+    const detail::SoA s = detail::soa_xyz(surf);
+    const size_t S = (size_t)(D * I);
+    std::vector<float> si(ns), h(nq * S);
+    for (size_t i = 0; i < ns; ++i) si[i] = surf.points[i].intensity;
+    // (the centres are the first nq surface points: the arrays' own prefixes)
+    if (!detail::ok(pfx_intensity_spin(detail::context(), s.x.data(), s.y.data(), s.z.data(), si.data(), (int64_t)ns,
+                                       s.x.data(), s.y.data(), s.z.data(), (int64_t)nq, this->search_radius_, D, I,
+                                       sigma_, h.data()),
+                    "IntensitySpinEstimation"))
+      return;
+    out.resize(nq);
+    out.is_dense = true;
+    for (size_t i = 0; i < nq; ++i) {
+      for (size_t b = 0; b < S; ++b) {
+        out.points[i].histogram[b] = h[i * S + b];
+        if (std::isnan(h[i * S + b])) out.is_dense = false;
+      }
+    }
+  }
+  int nr_distance_bins_ = 4, nr_intensity_bins_ = 5;
+  float sigma_ = 1.0f;
 };
 
 // ---- 3D shape contexts (evaluation.cpp:319-371) ------------------------------------------------

@@ -1,7 +1,7 @@
 """pcl_feature_extraction_amd -- MI355X-native (gfx950) hot path of srv/pcl_feature_extraction.
 
 NARF keypoints on the planar range image + normals + FPFH-33 / SHOT-352 / SHOT-1344 / PFH-125 / spin-image /
-intensity-gradient / RIFT / 3D-shape-context / unique-shape-context / moment-invariant / principal-curvature descriptors over radius neighbourhoods, descriptor matching, RANSAC rejection and ICP
+intensity-gradient / RIFT / intensity-spin / 3D-shape-context / unique-shape-context / moment-invariant / principal-curvature descriptors over radius neighbourhoods, descriptor matching, RANSAC rejection and ICP
 alignment, as hand-written HIP kernels behind the C-ABI in include/pfx.h (libpfx.so).
 See DESIGN.md.
 """

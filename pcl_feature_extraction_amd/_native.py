@@ -153,6 +153,10 @@ _SIGS = {
                          ctypes.c_int32, ctypes.c_int32, c_vp]),
     "pfx_rift_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
                              ctypes.c_int32, ctypes.c_int32, c_vp]),
+    "pfx_intensity_spin": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
+                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_vp]),
+    "pfx_intensity_spin_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
+                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_vp]),
     "pfx_moment_invariants": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl, c_vp]),
     "pfx_moment_invariants_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl, c_vp]),
     "pfx_principal_curvatures": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
@@ -223,11 +227,12 @@ _SIGS = {
 }
 
 # entry points an older library loaded through PFX_LIB (A/B runs against a previous build) may lack:
-# test hooks, ICP, spin images, intensity gradients, RIFT, the shape contexts, moment invariants and
-# principal curvatures (calling a missing one raises AttributeError there)
+# test hooks, ICP, spin images, intensity gradients, RIFT, intensity spin images, the shape contexts,
+# moment invariants and principal curvatures (calling a missing one raises AttributeError there)
 _OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_icp_dev",
                    "pfx_spin_params_default", "pfx_spin_image", "pfx_spin_image_dev",
                    "pfx_intensity_gradient", "pfx_intensity_gradient_dev", "pfx_rift", "pfx_rift_dev",
+                   "pfx_intensity_spin", "pfx_intensity_spin_dev",
                    "pfx_shape_context", "pfx_shape_context_dev", "pfx_usc", "pfx_usc_dev", "pfx_shot_lrf",
                    "pfx_shot_lrf_dev", "pfx_rng_uniform01", "pfx_moment_invariants", "pfx_moment_invariants_dev",
                    "pfx_principal_curvatures", "pfx_principal_curvatures_dev"}

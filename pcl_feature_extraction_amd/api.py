@@ -311,6 +311,19 @@ class Context:
                                        _ptr(cx), _ptr(cy), _ptr(cz), nq, float(r), D, G, _ptr(out)))
         return out
 
+    def intensity_spin(self, sx, sy, sz, si, cx, cy, cz, r, nr_distance_bins=4, nr_intensity_bins=5, sigma=1.0):
+        """IntensitySpinEstimation (pfx_intensity_spin): (nq, D I) float32, row[distance_bin * I +
+        intensity_bin]; si is the surface's intensity (rgb_to_intensity), (cx, cy, cz) the centres; a
+        NaN row for a centre without neighbours.  No normals are read."""
+        sx, sy, sz, si, cx, cy, cz = map(_f32, (sx, sy, sz, si, cx, cy, cz))
+        if len(si) != len(sx):
+            raise ValueError("intensity_spin: one intensity per surface point")
+        nq, D, I = len(cx), int(nr_distance_bins), int(nr_intensity_bins)  # noqa: E741
+        out = np.empty((nq, D * I if 1 <= D <= 16 and 1 <= I <= 16 else 1), dtype=np.float32)
+        self._check(self._lib.pfx_intensity_spin(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(si), len(sx), _ptr(cx),
+                                                 _ptr(cy), _ptr(cz), nq, float(r), D, I, float(sigma), _ptr(out)))
+        return out
+
     def moment_invariants(self, sx, sy, sz, qx, qy, qz, r):
         """MomentInvariantsEstimation (pfx_moment_invariants): (nq, 3) float32, j1 j2 j3 of the radius
         neighbours of each query; a NaN row for a query without neighbours."""
@@ -569,6 +582,15 @@ class Context:
         self._check(self._lib.pfx_rift_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(sgx), _ptr(sgy), _ptr(sgz),
                                            sx.numel(), _ptr(cx), _ptr(cy), _ptr(cz), cx.numel(), float(r),
                                            int(nr_distance_bins), int(nr_gradient_bins), _ptr(out)))
+
+    def intensity_spin_dev(self, sx, sy, sz, si, cx, cy, cz, r, out, nr_distance_bins=4, nr_intensity_bins=5,
+                           sigma=1.0):
+        """pfx_intensity_spin_dev: out is an (nq, D I) float32 device tensor; no host synchronisation
+        (a neighbourhood beyond capacity is reported by the next synchronize())."""
+        self._check(self._lib.pfx_intensity_spin_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(si), sx.numel(),
+                                                     _ptr(cx), _ptr(cy), _ptr(cz), cx.numel(), float(r),
+                                                     int(nr_distance_bins), int(nr_intensity_bins), float(sigma),
+                                                     _ptr(out)))
 
     def moment_invariants_dev(self, sx, sy, sz, qx, qy, qz, r, out):
         """pfx_moment_invariants_dev: out is an (nq, 3) float32 device tensor; no host synchronisation

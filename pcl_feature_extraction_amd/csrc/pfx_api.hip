@@ -147,6 +147,9 @@ pfx_status pfx_ctx_create(int device, pfx_ctx** out) {
     ctx->stats["spin_cap_small"] = pfx::spin_cap_small();
     ctx->stats["spin_chunk"] = pfx::spin_chunk();
     ctx->stats["rift_cap_small"] = pfx::rift_cap_small();
+    ctx->stats["ispin_cap_small"] = pfx::ispin_cap_small();
+    ctx->stats["ispin_tile_words"] = pfx::ispin_tile_words();
+    ctx->stats["ispin_tile"] = pfx::ispin_tile(20);  // of the default 4 x 5 image
     ctx->stats["sc_cap_small"] = pfx::sc_cap_small();
     ctx->stats["moments_cap_small"] = pfx::moments_cap_small();
     // grid builds by builder (pfx_grid.hip), and speculative counting builds that met a fat cell
@@ -792,6 +795,53 @@ pfx_status pfx_rift(pfx_ctx* ctx, const float* sx, const float* sy, const float*
   rows_out(ctx, out, dout, nq, S);
   PFX_HIP(hipStreamSynchronize(ctx->stream));
   pfx::reports_resolve(ctx, pfx::kRepIgrad, pfx::kRepRift);  // the host API reports at once
+  PFX_API_END(ctx)
+}
+
+// every check that precedes a launch (host and device entry points alike); the bound on sigma keeps
+// every int cast of the window in range
+static void ispin_check(const float* sx, const float* sy, const float* sz, const float* si, int64_t n_surface,
+                        const float* cx, const float* cy, const float* cz, int64_t nq, double radius, int D, int I,
+                        float sigma, const float* out) {
+  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!out || !cx || !cy || !cz)) ||
+      (n_surface && (!sx || !sy || !sz || !si)))
+    throw Error(PFX_ERR_INVALID, "intensity_spin: invalid arguments");
+  if (D < 1 || D > 16 || I < 1 || I > 16)
+    throw Error(PFX_ERR_INVALID, "intensity_spin: nr_distance_bins and nr_intensity_bins must be in [1, 16]");
+  if (!(sigma >= 0.0f && sigma <= 1048576.0f))
+    throw Error(PFX_ERR_INVALID, "intensity_spin: sigma must be in [0, 2^20]");
+}
+
+pfx_status pfx_intensity_spin_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                                  const float* d_si, int64_t n_surface, const float* d_cx, const float* d_cy,
+                                  const float* d_cz, int64_t nq, double radius, int32_t nr_distance_bins,
+                                  int32_t nr_intensity_bins, float sigma, float* d_out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  ispin_check(d_sx, d_sy, d_sz, d_si, n_surface, d_cx, d_cy, d_cz, nq, radius, nr_distance_bins, nr_intensity_bins,
+              sigma, d_out);
+  pfx::ispin_dev(ctx, d_sx, d_sy, d_sz, d_si, n_surface, d_cx, d_cy, d_cz, nq, radius, nr_distance_bins,
+                 nr_intensity_bins, sigma, d_out);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_intensity_spin(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* si,
+                              int64_t n_surface, const float* cx, const float* cy, const float* cz, int64_t nq,
+                              double radius, int32_t nr_distance_bins, int32_t nr_intensity_bins, float sigma,
+                              float* out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  ispin_check(sx, sy, sz, si, n_surface, cx, cy, cz, nq, radius, nr_distance_bins, nr_intensity_bins, sigma, out);
+  const int64_t S = (int64_t)nr_distance_bins * nr_intensity_bins;
+  const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface);
+  float* dsi = stage_in(ctx, "in_i", si, n_surface);
+  const Dev3 c = stage3(ctx, "in_q", cx, cy, cz, nq);
+  float* dout = ctx->buf("out_ispin").as<float>(nq * S + 1);
+  pfx::ispin_dev(ctx, s.x, s.y, s.z, dsi, n_surface, c.x, c.y, c.z, nq, radius, nr_distance_bins, nr_intensity_bins,
+                 sigma, dout);
+  rows_out(ctx, out, dout, nq, S);
+  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  pfx::reports_resolve(ctx, pfx::kRepIspin, pfx::kRepIspin);  // the host API reports at once
   PFX_API_END(ctx)
 }
 

@@ -131,7 +131,7 @@ struct GridView {
 // block in stream order, and they are read after the next synchronisation.  One slot per kind of
 // call, resolved in this order.
 enum ReportSlot {
-  kRepFpfh, kRepPfh, kRepSpin, kRepIgrad, kRepRift, kRepSc, kRepLrf, kRepMoments, kRepPcurv, kReportSlots
+  kRepFpfh, kRepPfh, kRepSpin, kRepIgrad, kRepRift, kRepIspin, kRepSc, kRepLrf, kRepMoments, kRepPcurv, kReportSlots
 };
 constexpr int kReportWords = 16;  // ints of a slot, on the device and in pinned memory
 struct Reports {
@@ -374,6 +374,7 @@ void pfh_report(pfx_ctx* ctx, const int* h);
 void spin_report(pfx_ctx* ctx, const int* h);
 void igrad_report(pfx_ctx* ctx, const int* h);
 void rift_report(pfx_ctx* ctx, const int* h);
+void ispin_report(pfx_ctx* ctx, const int* h);
 void sc_report(pfx_ctx* ctx, const int* h);
 void lrf_report(pfx_ctx* ctx, const int* h);
 void moments_report(pfx_ctx* ctx, const int* h);
@@ -424,6 +425,15 @@ void rift_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, c
               const float* sgy, const float* sgz, int64_t ns, const float* cx, const float* cy, const float* cz,
               int64_t nq, double r, int D, int G, float* out);
 int rift_cap_small();
+// intensity spin images (pfx_intensity_spin.hip): D x I bins, out[d * I + i]
+void ispin_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* si, int64_t ns,
+               const float* cx, const float* cy, const float* cz, int64_t nq, double r, int D, int I, float sigma,
+               float* out);
+int ispin_cap_small();
+// the weight tile: its floats (stat "ispin_tile_words") and the neighbours of a sub-chunk for S = D I
+// bins, min(256, words / (S | 1)) (stat "ispin_tile": of the default S = 20)
+int ispin_tile_words();
+int ispin_tile(int S);
 // 3D shape contexts, unique shape contexts and SHOT's frames alone (pfx_shape_context.hip).
 // sc_dev: frames == nullptr is the 3DSC (normals read; rnd nullable: the stream of seed 12345 from
 // its start), else USC.
