@@ -277,7 +277,9 @@ pfx_status pfx_normals_fast_dev(pfx_ctx* ctx, const float* d_x, const float* d_y
 
 /* ---- FPFH-33: FPFHEstimation (surface + normals, queries = input cloud) ------------- */
 /* same_as_surface != 0 selects PCL's "input_ == surface_ && indices == all" branch (queries
- * must then be the surface itself).  out: nq x 33 row-major (FPFHSignature33::histogram). */
+ * must then be the surface itself).  out: nq x 33 row-major (FPFHSignature33::histogram).
+ * A null surface or normal array with n_surface > 0, or a null query array with nq > 0 and
+ * same_as_surface == 0, is PFX_ERR_INVALID ("fpfh: invalid arguments") before any copy. */
 pfx_status pfx_fpfh(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz,
                     const float* snx, const float* sny, const float* snz, int64_t n_surface,
                     const float* qx, const float* qy, const float* qz, int64_t nq,
@@ -335,7 +337,9 @@ pfx_status pfx_fpfh_support_ball_dev(pfx_ctx* ctx, const float* d_sx, const floa
                                      const float* d_qz, int64_t nq, double radius, uint8_t* d_mask);
 
 /* ---- SHOT-352: SHOTEstimationOMP + SHOTLocalReferenceFrameEstimation ---------------- */
-/* desc: nq x 352, rf: nq x 9 (x_axis, y_axis, z_axis) -- SHOT352::{descriptor, rf}. */
+/* desc: nq x 352, rf: nq x 9 (x_axis, y_axis, z_axis) -- SHOT352::{descriptor, rf}.
+ * A null surface or normal array with n_surface > 0, or a null query array with nq > 0, is
+ * PFX_ERR_INVALID ("shot: invalid arguments") before any copy or launch, in both forms. */
 pfx_status pfx_shot(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz,
                     const float* snx, const float* sny, const float* snz, int64_t n_surface,
                     const float* qx, const float* qy, const float* qz, int64_t nq,

@@ -254,6 +254,8 @@ class PointCloud {
 namespace detail {
 struct SoA {
   std::vector<float> x, y, z;
+  size_t size() const { return x.size(); }
+  int64_t n() const { return (int64_t)x.size(); }  // the count as the C-ABI takes it
 };
 template <typename P>
 inline SoA soa_xyz(const PointCloud<P>& c) {
@@ -276,6 +278,27 @@ inline bool ok(pfx_status st, const char* who) {
   if (st == PFX_OK) return true;
   PCL_ERROR("[pcl::%s::compute] %s\n", who, context() ? pfx_last_error(context()) : "no device");
   return false;
+}
+// Which NaN of a row clears is_dense.  The C-ABI fills a row it could not compute with NaN, so its
+// first float tells; kAnyFloat is for the classes whose computed rows can hold a NaN as well (stricter
+// than PCL, which clears is_dense only for a row without neighbours).
+enum class NanRule { kFirstFloat, kAnyFloat };
+// The descriptor classes' one way from the C-ABI's rows to the output cloud: nq points, point i
+// taking WA floats of `a` and then WB floats of `b` (a descriptor and its rf) as its first floats.
+template <int WA, int WB = 0, typename PointOutT>
+inline void write_rows(PointCloud<PointOutT>& out, size_t nq, NanRule rule, const std::vector<float>& a,
+                       const std::vector<float>& b = std::vector<float>()) {
+  static_assert(sizeof(PointOutT) >= sizeof(float) * (WA + WB), "the output point holds the floats of a row");
+  out.resize(nq);
+  out.is_dense = true;
+  for (size_t i = 0; i < nq; ++i) {
+    float* row = reinterpret_cast<float*>(&out.points[i]);
+    std::copy(a.begin() + i * WA, a.begin() + (i + 1) * WA, row);
+    if (WB) std::copy(b.begin() + i * WB, b.begin() + (i + 1) * WB, row + WA);
+    const int tested = rule == NanRule::kAnyFloat ? WA + WB : 1;
+    for (int c = 0; c < tested; ++c)
+      if (std::isnan(row[c])) out.is_dense = false;
+  }
 }
 }  // namespace detail
 
@@ -324,6 +347,14 @@ class Feature {
   virtual void computeFeature(PointCloudOut& output) = 0;
   const PointCloudIn& surface() const { return surface_ ? *surface_ : *input_; }
   bool input_is_surface() const { return !surface_ || surface_.get() == input_.get(); }
+  // for the classes whose row i reads element i of something the surface has one of per point (a
+  // normal, a gradient, the point itself): more input points than surface points is an error
+  bool input_within_surface() const {
+    const size_t ns = surface().size();
+    if (input_->size() <= ns) return true;
+    PCL_ERROR("[pcl::%s::compute] input index %zu is beyond the search surface (%zu points)\n", name_.c_str(), ns, ns);
+    return false;
+  }
   std::string name_ = "Feature";
   PointCloudInConstPtr input_, surface_;
   KdTreePtr tree_;
@@ -339,6 +370,12 @@ class FeatureFromNormals : public Feature<PointInT, PointOutT> {
   void setInputNormals(const PointCloudNConstPtr& normals) { normals_ = normals; }
 
  protected:
+  // one normal per surface point, or PCL_ERROR with the class's own words for it
+  bool normals_match(const std::string& what) const {
+    if (normals_ && normals_->size() == this->surface().size()) return true;
+    PCL_ERROR("[pcl::%s::compute] %s\n", this->name_.c_str(), what.c_str());
+    return false;
+  }
   PointCloudNConstPtr normals_;
 };
 
@@ -385,26 +422,16 @@ class FPFHEstimation : public FeatureFromNormals<PointInT, PointNT, PointOutT> {
 
  protected:
   void computeFeature(PointCloud<PointOutT>& out) override {
-    const PointCloud<PointInT>& surf = this->surface();
-    if (!this->normals_ || this->normals_->size() != surf.size()) {
-      PCL_ERROR("[pcl::FPFHEstimation::compute] normals missing or not matching the surface\n");
-      return;
-    }
-    const detail::SoA s = detail::soa_xyz(surf), nrm = detail::soa_normals(*this->normals_);
+    if (!this->normals_match("normals missing or not matching the surface")) return;
+    const detail::SoA s = detail::soa_xyz(this->surface()), nrm = detail::soa_normals(*this->normals_);
     const detail::SoA q = detail::soa_xyz(*this->input_);
-    const size_t nq = this->input_->size();
-    std::vector<float> h(nq * 33);
+    std::vector<float> h(q.size() * 33);
     if (!detail::ok(pfx_fpfh(detail::context(), s.x.data(), s.y.data(), s.z.data(), nrm.x.data(), nrm.y.data(),
-                             nrm.z.data(), (int64_t)surf.size(), q.x.data(), q.y.data(), q.z.data(), (int64_t)nq,
+                             nrm.z.data(), s.n(), q.x.data(), q.y.data(), q.z.data(), q.n(),
                              this->input_is_surface() ? 1 : 0, this->search_radius_, h.data()),
                     "FPFHEstimation"))
       return;
-    out.resize(nq);
-    out.is_dense = true;
-    for (size_t i = 0; i < nq; ++i) {
-      for (int b = 0; b < 33; ++b) out.points[i].histogram[b] = h[i * 33 + b];
-      if (std::isnan(h[i * 33])) out.is_dense = false;
-    }
+    detail::write_rows<33>(out, q.size(), detail::NanRule::kFirstFloat, h);
   }
 };
 
@@ -418,26 +445,16 @@ class PFHEstimation : public FeatureFromNormals<PointInT, PointNT, PointOutT> {
 
  protected:
   void computeFeature(PointCloud<PointOutT>& out) override {
-    const PointCloud<PointInT>& surf = this->surface();
-    if (!this->normals_ || this->normals_->size() != surf.size()) {
-      PCL_ERROR("[pcl::PFHEstimation::compute] normals missing or not matching the surface\n");
-      return;
-    }
-    const detail::SoA s = detail::soa_xyz(surf), nrm = detail::soa_normals(*this->normals_);
+    if (!this->normals_match("normals missing or not matching the surface")) return;
+    const detail::SoA s = detail::soa_xyz(this->surface()), nrm = detail::soa_normals(*this->normals_);
     const detail::SoA q = detail::soa_xyz(*this->input_);
-    const size_t nq = this->input_->size();
-    std::vector<float> h(nq * 125);
+    std::vector<float> h(q.size() * 125);
     if (!detail::ok(pfx_pfh(detail::context(), s.x.data(), s.y.data(), s.z.data(), nrm.x.data(), nrm.y.data(),
-                            nrm.z.data(), (int64_t)surf.size(), q.x.data(), q.y.data(), q.z.data(), (int64_t)nq,
-                            this->search_radius_, h.data()),
+                            nrm.z.data(), s.n(), q.x.data(), q.y.data(), q.z.data(), q.n(), this->search_radius_,
+                            h.data()),
                     "PFHEstimation"))
       return;
-    out.resize(nq);
-    out.is_dense = true;
-    for (size_t i = 0; i < nq; ++i) {
-      for (int b = 0; b < 125; ++b) out.points[i].histogram[b] = h[i * 125 + b];
-      if (std::isnan(h[i * 125])) out.is_dense = false;
-    }
+    detail::write_rows<125>(out, q.size(), detail::NanRule::kFirstFloat, h);
   }
 };
 
@@ -452,27 +469,16 @@ class SHOTEstimationOMP : public FeatureFromNormals<PointInT, PointNT, PointOutT
 
  protected:
   void computeFeature(PointCloud<PointOutT>& out) override {
-    const PointCloud<PointInT>& surf = this->surface();
-    if (!this->normals_ || this->normals_->size() != surf.size()) {
-      PCL_ERROR("[pcl::SHOTEstimationOMP::compute] normals missing or not matching the surface\n");
-      return;
-    }
-    const detail::SoA s = detail::soa_xyz(surf), nrm = detail::soa_normals(*this->normals_);
+    if (!this->normals_match("normals missing or not matching the surface")) return;
+    const detail::SoA s = detail::soa_xyz(this->surface()), nrm = detail::soa_normals(*this->normals_);
     const detail::SoA q = detail::soa_xyz(*this->input_);
-    const size_t nq = this->input_->size();
-    std::vector<float> d(nq * 352), rf(nq * 9);
+    std::vector<float> d(q.size() * 352), rf(q.size() * 9);
     if (!detail::ok(pfx_shot(detail::context(), s.x.data(), s.y.data(), s.z.data(), nrm.x.data(), nrm.y.data(),
-                             nrm.z.data(), (int64_t)surf.size(), q.x.data(), q.y.data(), q.z.data(), (int64_t)nq,
-                             this->search_radius_, d.data(), rf.data()),
+                             nrm.z.data(), s.n(), q.x.data(), q.y.data(), q.z.data(), q.n(), this->search_radius_,
+                             d.data(), rf.data()),
                     "SHOTEstimationOMP"))
       return;
-    out.resize(nq);
-    out.is_dense = true;
-    for (size_t i = 0; i < nq; ++i) {
-      for (int b = 0; b < 352; ++b) out.points[i].descriptor[b] = d[i * 352 + b];
-      for (int b = 0; b < 9; ++b) out.points[i].rf[b] = rf[i * 9 + b];
-      if (std::isnan(d[i * 352])) out.is_dense = false;
-    }
+    detail::write_rows<352, 9>(out, q.size(), detail::NanRule::kFirstFloat, d, rf);
   }
 };
 
@@ -490,10 +496,7 @@ class SHOTColorEstimationOMP : public FeatureFromNormals<PointInT, PointNT, Poin
  protected:
   void computeFeature(PointCloud<PointOutT>& out) override {
     const PointCloud<PointInT>& surf = this->surface();
-    if (!this->normals_ || this->normals_->size() != surf.size()) {
-      PCL_ERROR("[pcl::SHOTColorEstimationOMP::compute] normals missing or not matching the surface\n");
-      return;
-    }
+    if (!this->normals_match("normals missing or not matching the surface")) return;
     const detail::SoA s = detail::soa_xyz(surf), nrm = detail::soa_normals(*this->normals_);
     const detail::SoA q = detail::soa_xyz(*this->input_);
     const size_t ns = surf.size(), nq = this->input_->size();
@@ -502,17 +505,11 @@ class SHOTColorEstimationOMP : public FeatureFromNormals<PointInT, PointNT, Poin
     for (size_t i = 0; i < nq; ++i) qrgb[i] = this->input_->points[i].rgba & 0x00ffffffu;
     std::vector<float> d(nq * 1344), rf(nq * 9);
     if (!detail::ok(pfx_shot_color(detail::context(), s.x.data(), s.y.data(), s.z.data(), nrm.x.data(),
-                                   nrm.y.data(), nrm.z.data(), srgb.data(), (int64_t)ns, q.x.data(), q.y.data(),
-                                   q.z.data(), qrgb.data(), (int64_t)nq, this->search_radius_, d.data(), rf.data()),
+                                   nrm.y.data(), nrm.z.data(), srgb.data(), s.n(), q.x.data(), q.y.data(), q.z.data(),
+                                   qrgb.data(), q.n(), this->search_radius_, d.data(), rf.data()),
                     "SHOTColorEstimationOMP"))
       return;
-    out.resize(nq);
-    out.is_dense = true;
-    for (size_t i = 0; i < nq; ++i) {
-      for (int b = 0; b < 1344; ++b) out.points[i].descriptor[b] = d[i * 1344 + b];
-      for (int b = 0; b < 9; ++b) out.points[i].rf[b] = rf[i * 9 + b];
-      if (std::isnan(d[i * 1344])) out.is_dense = false;
-    }
+    detail::write_rows<1344, 9>(out, nq, detail::NanRule::kFirstFloat, d, rf);
   }
 };
 
@@ -576,8 +573,7 @@ class SpinImageEstimation : public Feature<PointInT, PointOutT> {
                 "surface\n");
       return;
     }
-    const PointCloud<PointInT>& surf = this->surface();
-    const detail::SoA s = detail::soa_xyz(surf), q = detail::soa_xyz(*this->input_);
+    const detail::SoA s = detail::soa_xyz(this->surface()), q = detail::soa_xyz(*this->input_);
     const detail::SoA ax = detail::soa_normals(*input_normals_);
     pfx_spin_params prm;
     pfx_spin_params_default(&prm);
@@ -587,19 +583,14 @@ class SpinImageEstimation : public Feature<PointInT, PointOutT> {
     std::vector<float> h(nq * (size_t)S);
     const pfx_status st = pfx_spin_image(
         detail::context(), s.x.data(), s.y.data(), s.z.data(), support ? ax.x.data() : nullptr,
-        support ? ax.y.data() : nullptr, support ? ax.z.data() : nullptr, (int64_t)surf.size(), q.x.data(), q.y.data(),
-        q.z.data(), ax.x.data(), ax.y.data(), ax.z.data(), (int64_t)nq, this->search_radius_, &prm, h.data(), nullptr,
-        nullptr);
+        support ? ax.y.data() : nullptr, support ? ax.z.data() : nullptr, s.n(), q.x.data(), q.y.data(), q.z.data(),
+        ax.x.data(), ax.y.data(), ax.z.data(), q.n(), this->search_radius_, &prm, h.data(), nullptr, nullptr);
     // (every argument was checked above: PFX_ERR_INVALID is one of the two rules PCL throws on)
     if (st == PFX_ERR_INVALID)
       throw PCLException(std::string("[pcl::SpinImageEstimation::compute] ") + pfx_last_error(detail::context()));
     if (!detail::ok(st, "SpinImageEstimation")) return;
-    out.resize(nq);
-    out.is_dense = true;
-    for (size_t i = 0; i < nq; ++i) {
-      for (int64_t b = 0; b < S; ++b) out.points[i].histogram[b] = h[i * (size_t)S + (size_t)b];
-      if (std::isnan(h[i * (size_t)S])) out.is_dense = false;
-    }
+    // (S floats a row: the output histogram's own size, as checked above)
+    detail::write_rows<sizeof(PointOutT) / sizeof(float)>(out, nq, detail::NanRule::kFirstFloat, h);
   }
   PointCloudNConstPtr input_normals_;
   unsigned int image_width_;
@@ -653,16 +644,8 @@ class IntensityGradientEstimation : public FeatureFromNormals<PointInT, PointNT,
   void computeFeature(PointCloud<PointOutT>& out) override {
     const PointCloud<PointInT>& surf = this->surface();
     const size_t nq = this->input_->size(), ns = surf.size();
-    if (!this->normals_ || this->normals_->size() != ns) {
-      PCL_ERROR("[pcl::IntensityGradientEstimation::compute] the input normals are missing or do not match the "
-                "search surface\n");
-      return;
-    }
-    if (nq > ns) {  // row i reads normals_[i]
-      PCL_ERROR("[pcl::IntensityGradientEstimation::compute] input index %zu is beyond the search surface "
-                "(%zu points)\n", ns, ns);
-      return;
-    }
+    if (!this->normals_match("the input normals are missing or do not match the search surface")) return;
+    if (!this->input_within_surface()) return;  // row i reads normals_[i]
     const bool same = this->input_is_surface();
     const detail::SoA s = detail::soa_xyz(surf), q = same ? detail::SoA() : detail::soa_xyz(*this->input_);
     detail::SoA nrm = detail::soa_normals(*this->normals_);
@@ -672,17 +655,11 @@ class IntensityGradientEstimation : public FeatureFromNormals<PointInT, PointNT,
     for (size_t i = 0; i < ns; ++i) si[i] = intensity(surf.points[i]);
     const detail::SoA& qq = same ? s : q;
     if (!detail::ok(pfx_intensity_gradient(detail::context(), s.x.data(), s.y.data(), s.z.data(), si.data(),
-                                           (int64_t)ns, qq.x.data(), qq.y.data(), qq.z.data(), nrm.x.data(),
-                                           nrm.y.data(), nrm.z.data(), (int64_t)nq, same ? 1 : 0,
-                                           this->search_radius_, g.data()),
+                                           s.n(), qq.x.data(), qq.y.data(), qq.z.data(), nrm.x.data(), nrm.y.data(),
+                                           nrm.z.data(), (int64_t)nq, same ? 1 : 0, this->search_radius_, g.data()),
                     "IntensityGradientEstimation"))
       return;
-    out.resize(nq);
-    out.is_dense = true;
-    for (size_t i = 0; i < nq; ++i) {
-      for (int c = 0; c < 3; ++c) out.points[i].gradient[c] = g[3 * i + (size_t)c];
-      if (std::isnan(g[3 * i])) out.is_dense = false;
-    }
+    detail::write_rows<3>(out, nq, detail::NanRule::kFirstFloat, g);
   }
 };
 
@@ -697,24 +674,13 @@ class MomentInvariantsEstimation : public Feature<PointInT, PointOutT> {
 
  protected:
   void computeFeature(PointCloud<PointOutT>& out) override {
-    const PointCloud<PointInT>& surf = this->surface();
-    const size_t nq = this->input_->size(), ns = surf.size();
-    const detail::SoA s = detail::soa_xyz(surf), q = detail::soa_xyz(*this->input_);
-    std::vector<float> j(nq * 3);
-    if (!detail::ok(pfx_moment_invariants(detail::context(), s.x.data(), s.y.data(), s.z.data(), (int64_t)ns,
-                                          q.x.data(), q.y.data(), q.z.data(), (int64_t)nq, this->search_radius_,
-                                          j.data()),
+    const detail::SoA s = detail::soa_xyz(this->surface()), q = detail::soa_xyz(*this->input_);
+    std::vector<float> j(q.size() * 3);
+    if (!detail::ok(pfx_moment_invariants(detail::context(), s.x.data(), s.y.data(), s.z.data(), s.n(), q.x.data(),
+                                          q.y.data(), q.z.data(), q.n(), this->search_radius_, j.data()),
                     "MomentInvariantsEstimation"))
       return;
-    out.resize(nq);
-    out.is_dense = true;
-    for (size_t i = 0; i < nq; ++i) {
-      out.points[i].j1 = j[3 * i];
-      out.points[i].j2 = j[3 * i + 1];
-      out.points[i].j3 = j[3 * i + 2];
-      // (stricter than PCL, which clears is_dense only for a row without neighbours)
-      if (std::isnan(j[3 * i]) || std::isnan(j[3 * i + 1]) || std::isnan(j[3 * i + 2])) out.is_dense = false;
-    }
+    detail::write_rows<3>(out, q.size(), detail::NanRule::kAnyFloat, j);
   }
 };
 
@@ -732,38 +698,19 @@ class PrincipalCurvaturesEstimation : public FeatureFromNormals<PointInT, PointN
 
  protected:
   void computeFeature(PointCloud<PointOutT>& out) override {
-    const PointCloud<PointInT>& surf = this->surface();
-    const size_t nq = this->input_->size(), ns = surf.size();
-    if (!this->normals_ || this->normals_->size() != ns) {
-      PCL_ERROR("[pcl::PrincipalCurvaturesEstimation::compute] the input normals are missing or do not match the "
-                "search surface\n");
-      return;
-    }
-    if (nq > ns) {  // row i reads normals_[i]
-      PCL_ERROR("[pcl::PrincipalCurvaturesEstimation::compute] input index %zu is beyond the search surface "
-                "(%zu points)\n", ns, ns);
-      return;
-    }
-    const detail::SoA s = detail::soa_xyz(surf), q = detail::soa_xyz(*this->input_);
+    if (!this->normals_match("the input normals are missing or do not match the search surface")) return;
+    if (!this->input_within_surface()) return;  // row i reads normals_[i]
+    const detail::SoA s = detail::soa_xyz(this->surface()), q = detail::soa_xyz(*this->input_);
     const detail::SoA nrm = detail::soa_normals(*this->normals_);
-    std::vector<float> pc(nq * 5);
+    std::vector<float> pc(q.size() * 5);
     // (the query normals are the first nq surface normals: the arrays' own prefixes)
     if (!detail::ok(pfx_principal_curvatures(detail::context(), s.x.data(), s.y.data(), s.z.data(), nrm.x.data(),
-                                             nrm.y.data(), nrm.z.data(), (int64_t)ns, q.x.data(), q.y.data(),
-                                             q.z.data(), nrm.x.data(), nrm.y.data(), nrm.z.data(), (int64_t)nq,
-                                             this->search_radius_, pc.data()),
+                                             nrm.y.data(), nrm.z.data(), s.n(), q.x.data(), q.y.data(), q.z.data(),
+                                             nrm.x.data(), nrm.y.data(), nrm.z.data(), q.n(), this->search_radius_,
+                                             pc.data()),
                     "PrincipalCurvaturesEstimation"))
       return;
-    out.resize(nq);
-    out.is_dense = true;
-    for (size_t i = 0; i < nq; ++i) {
-      for (int c = 0; c < 3; ++c) out.points[i].principal_curvature[c] = pc[5 * i + (size_t)c];
-      out.points[i].pc1 = pc[5 * i + 3];
-      out.points[i].pc2 = pc[5 * i + 4];
-      // (stricter than PCL, which clears is_dense only for a row without neighbours)
-      for (int c = 0; c < 5; ++c)
-        if (std::isnan(pc[5 * i + (size_t)c])) out.is_dense = false;
-    }
+    detail::write_rows<5>(out, q.size(), detail::NanRule::kAnyFloat, pc);
   }
 };
 
@@ -798,10 +745,7 @@ class RIFTEstimation : public Feature<PointInT, PointOutT> {
                 "surface's\n");
       return;
     }
-    if (nq > ns) {  // row i reads surface_[i]
-      PCL_ERROR("[pcl::RIFTEstimation::compute] input index %zu is beyond the search surface (%zu points)\n", ns, ns);
-      return;
-    }
+    if (!this->input_within_surface()) return;  // row i reads surface_[i]
     if (D < 1 || D > 16 || G < 1 || G > 16 || (size_t)(D * G) != sizeof(PointOutT) / sizeof(float)) {
       PCL_ERROR("[pcl::RIFTEstimation::compute] nr_distance_bins * nr_gradient_bins = %d does not match the "
                 "output histogram (each in [1, 16])\n", D * G);
@@ -816,17 +760,12 @@ class RIFTEstimation : public Feature<PointInT, PointOutT> {
     }
     // (the centres are the first nq surface points: the arrays' own prefixes)
     if (!detail::ok(pfx_rift(detail::context(), s.x.data(), s.y.data(), s.z.data(), gx.data(), gy.data(), gz.data(),
-                             (int64_t)ns, s.x.data(), s.y.data(), s.z.data(), (int64_t)nq, this->search_radius_, D, G,
+                             s.n(), s.x.data(), s.y.data(), s.z.data(), (int64_t)nq, this->search_radius_, D, G,
                              h.data()),
                     "RIFTEstimation"))
       return;
-    out.resize(nq);
-    out.is_dense = true;
-    const size_t S = (size_t)(D * G);
-    for (size_t i = 0; i < nq; ++i) {
-      for (size_t b = 0; b < S; ++b) out.points[i].histogram[b] = h[i * S + b];
-      if (std::isnan(h[i * S])) out.is_dense = false;
-    }
+    // (D * G floats a row: the output histogram's own size, as checked above)
+    detail::write_rows<sizeof(PointOutT) / sizeof(float)>(out, nq, detail::NanRule::kFirstFloat, h);
   }
   PointCloudGradientConstPtr gradient_;
   int nr_distance_bins_ = 4, nr_gradient_bins_ = 4;
@@ -856,11 +795,7 @@ class IntensitySpinEstimation : public Feature<PointInT, PointOutT> {
     const PointCloud<PointInT>& surf = this->surface();
     const size_t nq = this->input_->size(), ns = surf.size();
     const int D = nr_distance_bins_, I = nr_intensity_bins_;
-    if (nq > ns) {  // row i reads surface_[i]
-      PCL_ERROR("[pcl::IntensitySpinEstimation::compute] input index %zu is beyond the search surface (%zu points)\n",
-                ns, ns);
-      return;
-    }
+    if (!this->input_within_surface()) return;  // row i reads surface_[i]
     if (D < 1 || D > 16 || I < 1 || I > 16 || (size_t)(D * I) != sizeof(PointOutT) / sizeof(float)) {
       PCL_ERROR("[pcl::IntensitySpinEstimation::compute] nr_distance_bins * nr_intensity_bins = %d does not match "
                 "the output histogram (each in [1, 16])\n", D * I);
@@ -871,19 +806,13 @@ class IntensitySpinEstimation : public Feature<PointInT, PointOutT> {
     std::vector<float> si(ns), h(nq * S);
     for (size_t i = 0; i < ns; ++i) si[i] = surf.points[i].intensity;
     // (the centres are the first nq surface points: the arrays' own prefixes)
-    if (!detail::ok(pfx_intensity_spin(detail::context(), s.x.data(), s.y.data(), s.z.data(), si.data(), (int64_t)ns,
+    if (!detail::ok(pfx_intensity_spin(detail::context(), s.x.data(), s.y.data(), s.z.data(), si.data(), s.n(),
                                        s.x.data(), s.y.data(), s.z.data(), (int64_t)nq, this->search_radius_, D, I,
                                        sigma_, h.data()),
                     "IntensitySpinEstimation"))
       return;
-    out.resize(nq);
-    out.is_dense = true;
-    for (size_t i = 0; i < nq; ++i) {
-      for (size_t b = 0; b < S; ++b) {
-        out.points[i].histogram[b] = h[i * S + b];
-        if (std::isnan(h[i * S + b])) out.is_dense = false;
-      }
-    }
+    // (S floats a row: the output histogram's own size, as checked above)
+    detail::write_rows<sizeof(PointOutT) / sizeof(float)>(out, nq, detail::NanRule::kAnyFloat, h);
   }
   int nr_distance_bins_ = 4, nr_intensity_bins_ = 5;
   float sigma_ = 1.0f;
@@ -891,17 +820,6 @@ class IntensitySpinEstimation : public Feature<PointInT, PointOutT> {
 
 // ---- 3D shape contexts (evaluation.cpp:319-371) ------------------------------------------------
 namespace detail {
-template <typename PointOutT>
-inline void sc_rows(const std::vector<float>& d, const std::vector<float>& rf, size_t nq, PointCloud<PointOutT>& out) {
-  static_assert(sizeof(PointOutT) == sizeof(float) * (1980 + 9), "a ShapeContext1980 output");
-  out.resize(nq);
-  out.is_dense = true;
-  for (size_t i = 0; i < nq; ++i) {
-    for (int b = 0; b < 1980; ++b) out.points[i].descriptor[b] = d[i * 1980 + b];
-    for (int b = 0; b < 9; ++b) out.points[i].rf[b] = rf[i * 9 + b];
-    if (std::isnan(d[i * 1980])) out.is_dense = false;
-  }
-}
 // PCL's initCompute rule of both shape contexts
 inline bool sc_radii_ok(const char* who, double radius, double min_radius, double density_radius) {
   if (radius < min_radius || !(min_radius > 0.0) || !(density_radius > 0.0)) {
@@ -938,28 +856,27 @@ class ShapeContext3DEstimation : public FeatureFromNormals<PointInT, PointNT, Po
     const PointCloud<PointInT>& surf = this->surface();
     if (!detail::sc_radii_ok("ShapeContext3DEstimation", this->search_radius_, min_radius_, point_density_radius_))
       return;
-    if (!this->normals_ || this->normals_->size() != surf.size()) {
-      PCL_ERROR("[pcl::ShapeContext3DEstimation::compute] the normals are missing or their number (%zu) differs from "
-                "the search surface's points (%zu): a row's frame is the normal at its nearest surface point\n",
-                this->normals_ ? this->normals_->size() : (size_t)0, surf.size());
+    if (!this->normals_match("the normals are missing or their number (" +
+                             std::to_string(this->normals_ ? this->normals_->size() : (size_t)0) +
+                             ") differs from the search surface's points (" + std::to_string(surf.size()) +
+                             "): a row's frame is the normal at its nearest surface point"))
       return;
-    }
     const detail::SoA s = detail::soa_xyz(surf), nrm = detail::soa_normals(*this->normals_);
     const detail::SoA q = detail::soa_xyz(*this->input_);
-    const size_t nq = this->input_->size();
+    const size_t nq = q.size();
     std::vector<float> d(nq * 1980), rf(nq * 9), rnd(nq * 3);
     // drawn ahead: three floats for every row; the rows that draw take them in order
     pfx_rng_uniform01(seed_, stream_pos_, (int64_t)rnd.size(), rnd.data());
     if (!detail::ok(pfx_shape_context(detail::context(), s.x.data(), s.y.data(), s.z.data(), nrm.x.data(),
-                                      nrm.y.data(), nrm.z.data(), (int64_t)surf.size(), q.x.data(), q.y.data(),
-                                      q.z.data(), (int64_t)nq, this->search_radius_, min_radius_,
-                                      point_density_radius_, rnd.data(), d.data(), rf.data()),
+                                      nrm.y.data(), nrm.z.data(), s.n(), q.x.data(), q.y.data(), q.z.data(), q.n(),
+                                      this->search_radius_, min_radius_, point_density_radius_, rnd.data(), d.data(),
+                                      rf.data()),
                     "ShapeContext3DEstimation"))
       return;
     int64_t draws = 0;
     if (!detail::ok(pfx_ctx_last_stats(detail::context(), "sc_draws", &draws), "ShapeContext3DEstimation")) return;
     stream_pos_ += 3 * draws;
-    detail::sc_rows(d, rf, nq, out);
+    detail::write_rows<1980, 9>(out, nq, detail::NanRule::kFirstFloat, d, rf);
   }
   double min_radius_ = 0.1, point_density_radius_ = 0.2;
   uint32_t seed_;
@@ -977,24 +894,14 @@ class SHOTLocalReferenceFrameEstimation : public Feature<PointInT, PointOutT> {
 
  protected:
   void computeFeature(PointCloud<PointOutT>& out) override {
-    static_assert(sizeof(PointOutT) == sizeof(float) * 9, "a ReferenceFrame output");
     const detail::SoA s = detail::soa_xyz(this->surface()), q = detail::soa_xyz(*this->input_);
-    const size_t nq = this->input_->size();
-    std::vector<float> rf(nq * 9);
-    if (!detail::ok(pfx_shot_lrf(detail::context(), s.x.data(), s.y.data(), s.z.data(), (int64_t)s.x.size(),
-                                 q.x.data(), q.y.data(), q.z.data(), (int64_t)nq, this->search_radius_, rf.data()),
+    std::vector<float> rf(q.size() * 9);
+    if (!detail::ok(pfx_shot_lrf(detail::context(), s.x.data(), s.y.data(), s.z.data(), s.n(), q.x.data(), q.y.data(),
+                                 q.z.data(), q.n(), this->search_radius_, rf.data()),
                     "SHOTLocalReferenceFrameEstimation"))
       return;
-    out.resize(nq);
-    out.is_dense = true;
-    for (size_t i = 0; i < nq; ++i) {
-      for (int b = 0; b < 3; ++b) {
-        out.points[i].x_axis[b] = rf[i * 9 + b];
-        out.points[i].y_axis[b] = rf[i * 9 + 3 + b];
-        out.points[i].z_axis[b] = rf[i * 9 + 6 + b];
-      }
-      if (std::isnan(rf[i * 9])) out.is_dense = false;
-    }
+    // (a ReferenceFrame is its x, y and z axes in a row, as the C-ABI's nine floats are)
+    detail::write_rows<9>(out, q.size(), detail::NanRule::kFirstFloat, rf);
   }
 };
 
@@ -1041,8 +948,8 @@ class UniqueShapeContext : public Feature<PointInT, PointOutT> {
         PCL_ERROR("[pcl::UniqueShapeContext::compute] the local radius must be positive\n");
         return;
       }
-      const pfx_status st = pfx_shot_lrf(detail::context(), s.x.data(), s.y.data(), s.z.data(), (int64_t)s.x.size(),
-                                         q.x.data(), q.y.data(), q.z.data(), (int64_t)nq, local_radius_, fr.data());
+      const pfx_status st = pfx_shot_lrf(detail::context(), s.x.data(), s.y.data(), s.z.data(), s.n(), q.x.data(),
+                                         q.y.data(), q.z.data(), q.n(), local_radius_, fr.data());
       if (st == PFX_ERR_CAPACITY) {
         PCL_ERROR("[pcl::UniqueShapeContext::compute] the reference frames at the local radius %g exceed the frame "
                   "search's capacity of 16384 neighbours (%s): set a smaller local radius with setLocalRadius or "
@@ -1051,12 +958,12 @@ class UniqueShapeContext : public Feature<PointInT, PointOutT> {
       }
       if (!detail::ok(st, "UniqueShapeContext")) return;
     }
-    if (!detail::ok(pfx_usc(detail::context(), s.x.data(), s.y.data(), s.z.data(), (int64_t)s.x.size(), q.x.data(),
-                            q.y.data(), q.z.data(), fr.data(), (int64_t)nq, this->search_radius_, min_radius_,
-                            point_density_radius_, d.data(), rf.data()),
+    if (!detail::ok(pfx_usc(detail::context(), s.x.data(), s.y.data(), s.z.data(), s.n(), q.x.data(), q.y.data(),
+                            q.z.data(), fr.data(), q.n(), this->search_radius_, min_radius_, point_density_radius_,
+                            d.data(), rf.data()),
                     "UniqueShapeContext"))
       return;
-    detail::sc_rows(d, rf, nq, out);
+    detail::write_rows<1980, 9>(out, nq, detail::NanRule::kFirstFloat, d, rf);
   }
   double min_radius_ = 0.1, point_density_radius_ = 0.2, local_radius_ = 2.5;
   PointCloudLRFConstPtr frames_;

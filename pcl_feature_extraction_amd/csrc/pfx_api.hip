@@ -71,6 +71,44 @@ void check_ctx(pfx_ctx* ctx) {
   }
 }
 
+// ---- what the descriptor entry points are written from ----------------------------------------
+// An argument rule (one *_rule per family, for its host and its device form alike) is written from
+// all_set over the triples and pointers a side needs, and args_rule for what every family asks:
+// counts >= 0, a side's pointers set where the side has rows, and `scalars_ok`, the radius test
+// where the family has one.  A family's own rules follow it in the *_rule, with their own texts.
+struct In3 {  // a caller's coordinate triple, host or device
+  const float *x, *y, *z;
+};
+bool is_set(const void* p) { return p != nullptr; }
+bool is_set(const In3& t) { return t.x && t.y && t.z; }
+template <class... A>
+bool all_set(const A&... a) {
+  return (... && is_set(a));
+}
+void args_rule(const char* name, int64_t n_surface, bool surface_set, int64_t nq, bool queries_set,
+               bool scalars_ok = true) {
+  if (n_surface < 0 || nq < 0 || !scalars_ok || (n_surface && !surface_set) || (nq && !queries_set))
+    throw Error(PFX_ERR_INVALID, std::string(name) + ": invalid arguments");
+}
+
+// The end of a host form: every output's nq rows back from its ctx-owned buffer in stream order,
+// the stream drained, and the family's deferred reports resolved where it posts any (the host API
+// reports at once)
+struct Rows {
+  template <class T>
+  Rows(T* host, const T* dev, int64_t width) : host(host), dev(dev), row_bytes(sizeof(T) * width) {}
+  void* host;  // nullable: not wanted
+  const void* dev;
+  size_t row_bytes;
+};
+constexpr pfx::ReportSlot kNoReports = pfx::kReportSlots;
+void finish_host(pfx_ctx* ctx, int64_t nq, std::initializer_list<Rows> outs, pfx::ReportSlot first = kNoReports,
+                 pfx::ReportSlot last = kNoReports) {
+  for (const Rows& o : outs) rows_out(ctx, (char*)o.host, (const char*)o.dev, nq, (int64_t)o.row_bytes);
+  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  if (first != kNoReports) pfx::reports_resolve(ctx, first, last);
+}
+
 // the host form of pfx_normals and pfx_normals_fast: stage, run `impl`, copy the four columns back
 using NormalsImpl = void (*)(pfx_ctx*, const float*, const float*, const float*, int64_t, double, const float*, float*,
                              float*, float*, float*);
@@ -445,17 +483,22 @@ pfx_status pfx_normals(pfx_ctx* ctx, const float* x, const float* y, const float
   PFX_API_END(ctx)
 }
 
+// FPFH's rule, with no radius test at the boundary.  `queries_set`: the device forms always need the
+// query arrays, the host form stages none under same_as_surface.
+static void fpfh_rule(In3 s, In3 n, int64_t n_surface, bool queries_set, int64_t nq, int same_as_surface,
+                      const float* out) {
+  args_rule("fpfh", n_surface, all_set(s, n), nq, queries_set && out);
+  if (same_as_surface && nq != n_surface)
+    throw Error(PFX_ERR_INVALID, "fpfh: same_as_surface requires nq == n_surface");
+}
+
 static void fpfh_dev_checked(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
                              const float* d_snx, const float* d_sny, const float* d_snz, int64_t n_surface,
                              const float* d_qx, const float* d_qy, const float* d_qz, int64_t nq,
                              int same_as_surface, double radius, float* d_out, bool after_normals) {
   check_ctx(ctx);
-  if (n_surface < 0 || nq < 0 || (nq && !d_out) ||
-      (n_surface && (!d_sx || !d_sy || !d_sz || !d_snx || !d_sny || !d_snz)) ||
-      (nq && (!d_qx || !d_qy || !d_qz)))
-    throw Error(PFX_ERR_INVALID, "fpfh: invalid arguments");
-  if (same_as_surface && nq != n_surface)
-    throw Error(PFX_ERR_INVALID, "fpfh: same_as_surface requires nq == n_surface");
+  fpfh_rule({d_sx, d_sy, d_sz}, {d_snx, d_sny, d_snz}, n_surface, all_set(d_qx, d_qy, d_qz), nq, same_as_surface,
+            d_out);
   pfx::fpfh_dev(ctx, d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, nq, same_as_surface,
                 radius, d_out, after_normals);
 }
@@ -508,16 +551,13 @@ pfx_status pfx_fpfh(pfx_ctx* ctx, const float* sx, const float* sy, const float*
                     const float* qz, int64_t nq, int same_as_surface, double radius, float* out) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  if (n_surface < 0 || nq < 0 || (nq && !out)) throw Error(PFX_ERR_INVALID, "fpfh: invalid arguments");
-  if (same_as_surface && nq != n_surface)
-    throw Error(PFX_ERR_INVALID, "fpfh: same_as_surface requires nq == n_surface");
+  fpfh_rule({sx, sy, sz}, {snx, sny, snz}, n_surface, same_as_surface || all_set(qx, qy, qz), nq, same_as_surface,
+            out);
   const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), n = stage3(ctx, "in_n", snx, sny, snz, n_surface);
   const Dev3 q = same_as_surface ? s : stage3(ctx, "in_q", qx, qy, qz, nq);
   float* dout = ctx->buf("out_fpfh").as<float>(nq * 33 + 1);
   pfx::fpfh_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, n_surface, q.x, q.y, q.z, nq, same_as_surface, radius, dout);
-  rows_out(ctx, out, dout, nq, 33);
-  PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::reports_resolve(ctx, pfx::kRepFpfh, pfx::kRepFpfh);  // the host API reports at once
+  finish_host(ctx, nq, {{out, dout, 33}}, pfx::kRepFpfh, pfx::kRepFpfh);
   PFX_API_END(ctx)
 }
 
@@ -545,14 +585,18 @@ pfx_status pfx_fpfh_support_ball_dev(pfx_ctx* ctx, const float* d_sx, const floa
   PFX_API_END(ctx)
 }
 
+// SHOT's rule, with no radius test at the boundary
+static void shot_rule(In3 s, In3 n, int64_t n_surface, In3 q, int64_t nq, const float* desc, const float* rf) {
+  args_rule("shot", n_surface, all_set(s, n), nq, all_set(q, desc, rf));
+}
+
 pfx_status pfx_shot_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
                         const float* d_snx, const float* d_sny, const float* d_snz, int64_t n_surface,
                         const float* d_qx, const float* d_qy, const float* d_qz, int64_t nq, double radius,
                         float* d_desc, float* d_rf) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  if (n_surface < 0 || nq < 0 || (nq && (!d_desc || !d_rf || !d_qx || !d_qy || !d_qz)))
-    throw Error(PFX_ERR_INVALID, "shot: invalid arguments");
+  shot_rule({d_sx, d_sy, d_sz}, {d_snx, d_sny, d_snz}, n_surface, {d_qx, d_qy, d_qz}, nq, d_desc, d_rf);
   pfx::shot_dev(ctx, d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, nq, radius, d_desc, d_rf);
   PFX_API_END(ctx)
 }
@@ -562,16 +606,19 @@ pfx_status pfx_shot(pfx_ctx* ctx, const float* sx, const float* sy, const float*
                     const float* qz, int64_t nq, double radius, float* desc, float* rf) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  if (n_surface < 0 || nq < 0 || (nq && (!desc || !rf))) throw Error(PFX_ERR_INVALID, "shot: invalid arguments");
+  shot_rule({sx, sy, sz}, {snx, sny, snz}, n_surface, {qx, qy, qz}, nq, desc, rf);
   const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), n = stage3(ctx, "in_n", snx, sny, snz, n_surface);
   const Dev3 q = stage3(ctx, "in_q", qx, qy, qz, nq);
   float* ddesc = ctx->buf("out_shot").as<float>(nq * 352 + 1);
   float* drf = ctx->buf("out_rf").as<float>(nq * 9 + 1);
   pfx::shot_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, n_surface, q.x, q.y, q.z, nq, radius, ddesc, drf);
-  rows_out(ctx, desc, ddesc, nq, 352);
-  rows_out(ctx, rf, drf, nq, 9);
-  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  finish_host(ctx, nq, {{desc, ddesc, 352}, {rf, drf, 9}});  // (SHOT posts no reports)
   PFX_API_END(ctx)
+}
+
+static void shot_color_rule(In3 s, In3 n, const uint32_t* srgb, int64_t n_surface, In3 q, const uint32_t* qrgb,
+                            int64_t nq, double radius, const float* desc, const float* rf) {
+  args_rule("shot_color", n_surface, all_set(s, n, srgb), nq, all_set(q, qrgb, desc, rf), radius > 0.0);
 }
 
 pfx_status pfx_shot_color_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
@@ -581,10 +628,8 @@ pfx_status pfx_shot_color_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy
                               double radius, float* d_desc, float* d_rf) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  if (n_surface < 0 || nq < 0 || !(radius > 0.0) ||
-      (nq && (!d_desc || !d_rf || !d_qx || !d_qy || !d_qz || !d_qrgb)) ||
-      (n_surface && (!d_sx || !d_sy || !d_sz || !d_snx || !d_sny || !d_snz || !d_srgb)))
-    throw Error(PFX_ERR_INVALID, "shot_color: invalid arguments");
+  shot_color_rule({d_sx, d_sy, d_sz}, {d_snx, d_sny, d_snz}, d_srgb, n_surface, {d_qx, d_qy, d_qz}, d_qrgb, nq,
+                  radius, d_desc, d_rf);
   pfx::shot_color_dev(ctx, d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, d_srgb, n_surface, d_qx, d_qy, d_qz, d_qrgb, nq,
                       radius, d_desc, d_rf);
   PFX_API_END(ctx)
@@ -596,9 +641,7 @@ pfx_status pfx_shot_color(pfx_ctx* ctx, const float* sx, const float* sy, const 
                           double radius, float* desc, float* rf) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!desc || !rf || !qx || !qy || !qz || !qrgb)) ||
-      (n_surface && (!sx || !sy || !sz || !snx || !sny || !snz || !srgb)))
-    throw Error(PFX_ERR_INVALID, "shot_color: invalid arguments");
+  shot_color_rule({sx, sy, sz}, {snx, sny, snz}, srgb, n_surface, {qx, qy, qz}, qrgb, nq, radius, desc, rf);
   const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), n = stage3(ctx, "in_n", snx, sny, snz, n_surface);
   // (the packed colours are staged as the 32-bit words they are)
   float* drgb = stage_in(ctx, "in_rgb", reinterpret_cast<const float*>(srgb), n_surface);
@@ -608,10 +651,12 @@ pfx_status pfx_shot_color(pfx_ctx* ctx, const float* sx, const float* sy, const 
   float* drf = ctx->buf("out_rf").as<float>(nq * 9 + 1);
   pfx::shot_color_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, reinterpret_cast<const uint32_t*>(drgb), n_surface, q.x, q.y,
                       q.z, reinterpret_cast<const uint32_t*>(dqrgb), nq, radius, ddesc, drf);
-  rows_out(ctx, desc, ddesc, nq, 1344);
-  rows_out(ctx, rf, drf, nq, 9);
-  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  finish_host(ctx, nq, {{desc, ddesc, 1344}, {rf, drf, 9}});  // (SHOT colour posts no reports)
   PFX_API_END(ctx)
+}
+
+static void pfh_rule(In3 s, In3 n, int64_t n_surface, In3 q, int64_t nq, double radius, const float* out) {
+  args_rule("pfh", n_surface, all_set(s, n), nq, all_set(q, out), radius > 0.0);
 }
 
 pfx_status pfx_pfh_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz, const float* d_snx,
@@ -619,9 +664,7 @@ pfx_status pfx_pfh_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const
                        const float* d_qy, const float* d_qz, int64_t nq, double radius, float* d_out) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!d_out || !d_qx || !d_qy || !d_qz)) ||
-      (n_surface && (!d_sx || !d_sy || !d_sz || !d_snx || !d_sny || !d_snz)))
-    throw Error(PFX_ERR_INVALID, "pfh: invalid arguments");
+  pfh_rule({d_sx, d_sy, d_sz}, {d_snx, d_sny, d_snz}, n_surface, {d_qx, d_qy, d_qz}, nq, radius, d_out);
   pfx::pfh_dev(ctx, d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, nq, radius, d_out);
   PFX_API_END(ctx)
 }
@@ -631,16 +674,12 @@ pfx_status pfx_pfh(pfx_ctx* ctx, const float* sx, const float* sy, const float* 
                    const float* qz, int64_t nq, double radius, float* out) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!out || !qx || !qy || !qz)) ||
-      (n_surface && (!sx || !sy || !sz || !snx || !sny || !snz)))
-    throw Error(PFX_ERR_INVALID, "pfh: invalid arguments");
+  pfh_rule({sx, sy, sz}, {snx, sny, snz}, n_surface, {qx, qy, qz}, nq, radius, out);
   const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), n = stage3(ctx, "in_n", snx, sny, snz, n_surface);
   const Dev3 q = stage3(ctx, "in_q", qx, qy, qz, nq);
   float* dout = ctx->buf("out_pfh").as<float>(nq * 125 + 1);
   pfx::pfh_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, n_surface, q.x, q.y, q.z, nq, radius, dout);
-  rows_out(ctx, out, dout, nq, 125);
-  PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::reports_resolve(ctx, pfx::kRepPfh, pfx::kRepPfh);  // the host API reports at once
+  finish_host(ctx, nq, {{out, dout, 125}}, pfx::kRepPfh, pfx::kRepPfh);
   PFX_API_END(ctx)
 }
 
@@ -653,14 +692,10 @@ void pfx_spin_params_default(pfx_spin_params* p) {
   p->angular = 0;
 }
 
-// every check that precedes a launch (host and device entry points alike)
-static void spin_check(const float* sx, const float* sy, const float* sz, const float* snx, const float* sny,
-                       const float* snz, int64_t n_surface, const float* qx, const float* qy, const float* qz,
-                       const float* qnx, const float* qny, const float* qnz, int64_t nq, double radius,
-                       const pfx_spin_params* p, const float* out) {
-  if (!p || n_surface < 0 || nq < 0 || !(radius > 0.0) ||
-      (nq && (!out || !qx || !qy || !qz || !qnx || !qny || !qnz)) || (n_surface && (!sx || !sy || !sz)))
-    throw Error(PFX_ERR_INVALID, "spin_image: invalid arguments");
+// (the surface normals are optional: needed only under a support angle)
+static void spin_rule(In3 s, In3 n, int64_t n_surface, In3 q, In3 qn, int64_t nq, double radius,
+                      const pfx_spin_params* p, const float* out) {
+  args_rule("spin_image", n_surface, all_set(s), nq, all_set(q, qn, out), p && radius > 0.0);
   if (p->radial != 0 || p->angular != 0)
     throw Error(PFX_ERR_UNSUPPORTED, "spin_image: the radial structure and the angular domain are not supported");
   if (p->image_width < 1 || p->image_width > 16)
@@ -668,7 +703,7 @@ static void spin_check(const float* sx, const float* sy, const float* sz, const 
   if (!(p->support_angle_cos >= 0.0 && p->support_angle_cos <= 1.0))
     throw Error(PFX_ERR_INVALID, "spin_image: support_angle_cos must be in [0, 1]");
   if (p->min_pts_neighb < 0) throw Error(PFX_ERR_INVALID, "spin_image: min_pts_neighb must be >= 0");
-  if (p->support_angle_cos > 0.0 && n_surface && (!snx || !sny || !snz))
+  if (p->support_angle_cos > 0.0 && n_surface && !all_set(n))
     throw Error(PFX_ERR_INVALID, "spin_image: a support angle needs the surface normals");
 }
 
@@ -679,8 +714,8 @@ pfx_status pfx_spin_image_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy
                               const pfx_spin_params* params, float* d_out, double* d_raw, double* d_sums) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  spin_check(d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, d_qnx, d_qny, d_qnz, nq, radius,
-             params, d_out);
+  spin_rule({d_sx, d_sy, d_sz}, {d_snx, d_sny, d_snz}, n_surface, {d_qx, d_qy, d_qz}, {d_qnx, d_qny, d_qnz}, nq,
+            radius, params, d_out);
   pfx::spin_dev(ctx, d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, d_qnx, d_qny, d_qnz, nq,
                 radius, *params, d_out, d_raw, d_sums);
   PFX_API_END(ctx)
@@ -692,7 +727,7 @@ pfx_status pfx_spin_image(pfx_ctx* ctx, const float* sx, const float* sy, const 
                           double radius, const pfx_spin_params* params, float* out, double* raw, double* sums) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  spin_check(sx, sy, sz, snx, sny, snz, n_surface, qx, qy, qz, qnx, qny, qnz, nq, radius, params, out);
+  spin_rule({sx, sy, sz}, {snx, sny, snz}, n_surface, {qx, qy, qz}, {qnx, qny, qnz}, nq, radius, params, out);
   const bool normals = params->support_angle_cos > 0.0 && n_surface;
   const int64_t S = (int64_t)(params->image_width + 1) * (2 * params->image_width + 1);
   const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface);
@@ -703,22 +738,15 @@ pfx_status pfx_spin_image(pfx_ctx* ctx, const float* sx, const float* sy, const 
   double* dsums = sums ? ctx->buf("out_spin_sums").as<double>(nq + 1) : nullptr;
   pfx::spin_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, n_surface, q.x, q.y, q.z, a.x, a.y, a.z, nq, radius, *params, dout,
                 draw, dsums);
-  rows_out(ctx, out, dout, nq, S);
-  rows_out(ctx, raw, draw, nq, S);
-  rows_out(ctx, sums, dsums, nq, 1);
-  PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::reports_resolve(ctx, pfx::kRepSpin, pfx::kRepSpin);  // the host API reports at once
+  finish_host(ctx, nq, {{out, dout, S}, {raw, draw, S}, {sums, dsums, 1}}, pfx::kRepSpin, pfx::kRepSpin);
   PFX_API_END(ctx)
 }
 
-// every check that precedes a launch (host and device entry points alike)
-static void igrad_check(const float* sx, const float* sy, const float* sz, const float* si, int64_t n_surface,
-                        const float* qx, const float* qy, const float* qz, const float* qnx, const float* qny,
-                        const float* qnz, int64_t nq, int same, bool dev, double radius, const float* out) {
-  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!out || !qx || !qy || !qz || !qnx || !qny || !qnz)) ||
-      (n_surface && (!sx || !sy || !sz || !si)))
-    throw Error(PFX_ERR_INVALID, "intensity_gradient: invalid arguments");
-  if (same && (nq != n_surface || (dev && (qx != sx || qy != sy || qz != sz))))
+// (`dev`: the device form tells the whole-cloud path by the pointers themselves)
+static void igrad_rule(In3 s, const float* si, int64_t n_surface, In3 q, In3 qn, int64_t nq, int same, bool dev,
+                       double radius, const float* out) {
+  args_rule("intensity_gradient", n_surface, all_set(s, si), nq, all_set(q, qn, out), radius > 0.0);
+  if (same && (nq != n_surface || (dev && (q.x != s.x || q.y != s.y || q.z != s.z))))
     throw Error(PFX_ERR_INVALID, "intensity_gradient: same_as_surface needs the queries to be the surface");
 }
 
@@ -728,8 +756,8 @@ pfx_status pfx_intensity_gradient_dev(pfx_ctx* ctx, const float* d_sx, const flo
                                       int64_t nq, int32_t same_as_surface, double radius, float* d_out) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  igrad_check(d_sx, d_sy, d_sz, d_si, n_surface, d_qx, d_qy, d_qz, d_qnx, d_qny, d_qnz, nq, same_as_surface, true,
-              radius, d_out);
+  igrad_rule({d_sx, d_sy, d_sz}, d_si, n_surface, {d_qx, d_qy, d_qz}, {d_qnx, d_qny, d_qnz}, nq, same_as_surface,
+             true, radius, d_out);
   pfx::igrad_dev(ctx, d_sx, d_sy, d_sz, d_si, n_surface, d_qx, d_qy, d_qz, d_qnx, d_qny, d_qnz, nq, same_as_surface,
                  radius, d_out);
   PFX_API_END(ctx)
@@ -741,7 +769,7 @@ pfx_status pfx_intensity_gradient(pfx_ctx* ctx, const float* sx, const float* sy
                                   int32_t same_as_surface, double radius, float* out) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  igrad_check(sx, sy, sz, si, n_surface, qx, qy, qz, qnx, qny, qnz, nq, same_as_surface, false, radius, out);
+  igrad_rule({sx, sy, sz}, si, n_surface, {qx, qy, qz}, {qnx, qny, qnz}, nq, same_as_surface, false, radius, out);
   const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface);
   float* dsi = stage_in(ctx, "in_i", si, n_surface);
   // (the whole-cloud path reads the surface's own arrays as its queries)
@@ -749,18 +777,13 @@ pfx_status pfx_intensity_gradient(pfx_ctx* ctx, const float* sx, const float* sy
   const Dev3 n = stage3(ctx, "in_qn", qnx, qny, qnz, nq);
   float* dout = ctx->buf("out_igrad").as<float>(nq * 3 + 1);
   pfx::igrad_dev(ctx, s.x, s.y, s.z, dsi, n_surface, q.x, q.y, q.z, n.x, n.y, n.z, nq, same_as_surface, radius, dout);
-  rows_out(ctx, out, dout, nq, 3);
-  PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::reports_resolve(ctx, pfx::kRepIgrad, pfx::kRepRift);  // the host API reports at once
+  finish_host(ctx, nq, {{out, dout, 3}}, pfx::kRepIgrad, pfx::kRepRift);
   PFX_API_END(ctx)
 }
 
-static void rift_check(const float* sx, const float* sy, const float* sz, const float* sgx, const float* sgy,
-                       const float* sgz, int64_t n_surface, const float* cx, const float* cy, const float* cz,
-                       int64_t nq, double radius, int D, int G, const float* out) {
-  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!out || !cx || !cy || !cz)) ||
-      (n_surface && (!sx || !sy || !sz || !sgx || !sgy || !sgz)))
-    throw Error(PFX_ERR_INVALID, "rift: invalid arguments");
+static void rift_rule(In3 s, In3 g, int64_t n_surface, In3 c, int64_t nq, double radius, int D, int G,
+                      const float* out) {
+  args_rule("rift", n_surface, all_set(s, g), nq, all_set(c, out), radius > 0.0);
   if (D < 1 || D > 16 || G < 1 || G > 16)
     throw Error(PFX_ERR_INVALID, "rift: nr_distance_bins and nr_gradient_bins must be in [1, 16]");
 }
@@ -771,8 +794,8 @@ pfx_status pfx_rift_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, cons
                         int32_t nr_gradient_bins, float* d_out) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  rift_check(d_sx, d_sy, d_sz, d_sgx, d_sgy, d_sgz, n_surface, d_cx, d_cy, d_cz, nq, radius, nr_distance_bins,
-             nr_gradient_bins, d_out);
+  rift_rule({d_sx, d_sy, d_sz}, {d_sgx, d_sgy, d_sgz}, n_surface, {d_cx, d_cy, d_cz}, nq, radius, nr_distance_bins,
+            nr_gradient_bins, d_out);
   pfx::rift_dev(ctx, d_sx, d_sy, d_sz, d_sgx, d_sgy, d_sgz, n_surface, d_cx, d_cy, d_cz, nq, radius,
                 nr_distance_bins, nr_gradient_bins, d_out);
   PFX_API_END(ctx)
@@ -784,7 +807,8 @@ pfx_status pfx_rift(pfx_ctx* ctx, const float* sx, const float* sy, const float*
                     float* out) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  rift_check(sx, sy, sz, sgx, sgy, sgz, n_surface, cx, cy, cz, nq, radius, nr_distance_bins, nr_gradient_bins, out);
+  rift_rule({sx, sy, sz}, {sgx, sgy, sgz}, n_surface, {cx, cy, cz}, nq, radius, nr_distance_bins, nr_gradient_bins,
+            out);
   const int64_t S = (int64_t)nr_distance_bins * nr_gradient_bins;
   // (the gradients ride in the normals' buffers)
   const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), g = stage3(ctx, "in_n", sgx, sgy, sgz, n_surface);
@@ -792,20 +816,14 @@ pfx_status pfx_rift(pfx_ctx* ctx, const float* sx, const float* sy, const float*
   float* dout = ctx->buf("out_rift").as<float>(nq * S + 1);
   pfx::rift_dev(ctx, s.x, s.y, s.z, g.x, g.y, g.z, n_surface, c.x, c.y, c.z, nq, radius, nr_distance_bins,
                 nr_gradient_bins, dout);
-  rows_out(ctx, out, dout, nq, S);
-  PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::reports_resolve(ctx, pfx::kRepIgrad, pfx::kRepRift);  // the host API reports at once
+  finish_host(ctx, nq, {{out, dout, S}}, pfx::kRepIgrad, pfx::kRepRift);
   PFX_API_END(ctx)
 }
 
-// every check that precedes a launch (host and device entry points alike); the bound on sigma keeps
-// every int cast of the window in range
-static void ispin_check(const float* sx, const float* sy, const float* sz, const float* si, int64_t n_surface,
-                        const float* cx, const float* cy, const float* cz, int64_t nq, double radius, int D, int I,
-                        float sigma, const float* out) {
-  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!out || !cx || !cy || !cz)) ||
-      (n_surface && (!sx || !sy || !sz || !si)))
-    throw Error(PFX_ERR_INVALID, "intensity_spin: invalid arguments");
+// (the bound on sigma keeps every int cast of the window in range)
+static void ispin_rule(In3 s, const float* si, int64_t n_surface, In3 c, int64_t nq, double radius, int D, int I,
+                       float sigma, const float* out) {
+  args_rule("intensity_spin", n_surface, all_set(s, si), nq, all_set(c, out), radius > 0.0);
   if (D < 1 || D > 16 || I < 1 || I > 16)
     throw Error(PFX_ERR_INVALID, "intensity_spin: nr_distance_bins and nr_intensity_bins must be in [1, 16]");
   if (!(sigma >= 0.0f && sigma <= 1048576.0f))
@@ -818,8 +836,8 @@ pfx_status pfx_intensity_spin_dev(pfx_ctx* ctx, const float* d_sx, const float* 
                                   int32_t nr_intensity_bins, float sigma, float* d_out) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  ispin_check(d_sx, d_sy, d_sz, d_si, n_surface, d_cx, d_cy, d_cz, nq, radius, nr_distance_bins, nr_intensity_bins,
-              sigma, d_out);
+  ispin_rule({d_sx, d_sy, d_sz}, d_si, n_surface, {d_cx, d_cy, d_cz}, nq, radius, nr_distance_bins,
+             nr_intensity_bins, sigma, d_out);
   pfx::ispin_dev(ctx, d_sx, d_sy, d_sz, d_si, n_surface, d_cx, d_cy, d_cz, nq, radius, nr_distance_bins,
                  nr_intensity_bins, sigma, d_out);
   PFX_API_END(ctx)
@@ -831,7 +849,7 @@ pfx_status pfx_intensity_spin(pfx_ctx* ctx, const float* sx, const float* sy, co
                               float* out) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  ispin_check(sx, sy, sz, si, n_surface, cx, cy, cz, nq, radius, nr_distance_bins, nr_intensity_bins, sigma, out);
+  ispin_rule({sx, sy, sz}, si, n_surface, {cx, cy, cz}, nq, radius, nr_distance_bins, nr_intensity_bins, sigma, out);
   const int64_t S = (int64_t)nr_distance_bins * nr_intensity_bins;
   const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface);
   float* dsi = stage_in(ctx, "in_i", si, n_surface);
@@ -839,18 +857,12 @@ pfx_status pfx_intensity_spin(pfx_ctx* ctx, const float* sx, const float* sy, co
   float* dout = ctx->buf("out_ispin").as<float>(nq * S + 1);
   pfx::ispin_dev(ctx, s.x, s.y, s.z, dsi, n_surface, c.x, c.y, c.z, nq, radius, nr_distance_bins, nr_intensity_bins,
                  sigma, dout);
-  rows_out(ctx, out, dout, nq, S);
-  PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::reports_resolve(ctx, pfx::kRepIspin, pfx::kRepIspin);  // the host API reports at once
+  finish_host(ctx, nq, {{out, dout, S}}, pfx::kRepIspin, pfx::kRepIspin);
   PFX_API_END(ctx)
 }
 
-// every check that precedes a launch (host and device entry points alike)
-static void moments_check(const float* sx, const float* sy, const float* sz, int64_t n_surface, const float* qx,
-                          const float* qy, const float* qz, int64_t nq, double radius, const float* out) {
-  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!out || !qx || !qy || !qz)) ||
-      (n_surface && (!sx || !sy || !sz)))
-    throw Error(PFX_ERR_INVALID, "moment_invariants: invalid arguments");
+static void moments_rule(In3 s, int64_t n_surface, In3 q, int64_t nq, double radius, const float* out) {
+  args_rule("moment_invariants", n_surface, all_set(s), nq, all_set(q, out), radius > 0.0);
 }
 
 pfx_status pfx_moment_invariants_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
@@ -858,7 +870,7 @@ pfx_status pfx_moment_invariants_dev(pfx_ctx* ctx, const float* d_sx, const floa
                                      int64_t nq, double radius, float* d_out) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  moments_check(d_sx, d_sy, d_sz, n_surface, d_qx, d_qy, d_qz, nq, radius, d_out);
+  moments_rule({d_sx, d_sy, d_sz}, n_surface, {d_qx, d_qy, d_qz}, nq, radius, d_out);
   pfx::moments_dev(ctx, d_sx, d_sy, d_sz, n_surface, d_qx, d_qy, d_qz, nq, radius, d_out);
   PFX_API_END(ctx)
 }
@@ -868,25 +880,18 @@ pfx_status pfx_moment_invariants(pfx_ctx* ctx, const float* sx, const float* sy,
                                  float* out) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  moments_check(sx, sy, sz, n_surface, qx, qy, qz, nq, radius, out);
-  if (nq) {
+  moments_rule({sx, sy, sz}, n_surface, {qx, qy, qz}, nq, radius, out);
+  if (nq) {  // (without queries nothing is staged, run or resolved)
     const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), q = stage3(ctx, "in_q", qx, qy, qz, nq);
     float* dout = ctx->buf("out_moments").as<float>(nq * 3 + 1);
     pfx::moments_dev(ctx, s.x, s.y, s.z, n_surface, q.x, q.y, q.z, nq, radius, dout);
-    rows_out(ctx, out, dout, nq, 3);
-    PFX_HIP(hipStreamSynchronize(ctx->stream));
-    pfx::reports_resolve(ctx, pfx::kRepMoments, pfx::kRepPcurv);  // the host API reports at once
+    finish_host(ctx, nq, {{out, dout, 3}}, pfx::kRepMoments, pfx::kRepPcurv);
   }
   PFX_API_END(ctx)
 }
 
-static void pcurv_check(const float* sx, const float* sy, const float* sz, const float* snx, const float* sny,
-                        const float* snz, int64_t n_surface, const float* qx, const float* qy, const float* qz,
-                        const float* qnx, const float* qny, const float* qnz, int64_t nq, double radius,
-                        const float* out) {
-  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!out || !qx || !qy || !qz || !qnx || !qny || !qnz)) ||
-      (n_surface && (!sx || !sy || !sz || !snx || !sny || !snz)))
-    throw Error(PFX_ERR_INVALID, "principal_curvatures: invalid arguments");
+static void pcurv_rule(In3 s, In3 n, int64_t n_surface, In3 q, In3 qn, int64_t nq, double radius, const float* out) {
+  args_rule("principal_curvatures", n_surface, all_set(s, n), nq, all_set(q, qn, out), radius > 0.0);
 }
 
 pfx_status pfx_principal_curvatures_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
@@ -896,8 +901,8 @@ pfx_status pfx_principal_curvatures_dev(pfx_ctx* ctx, const float* d_sx, const f
                                         double radius, float* d_out) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  pcurv_check(d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, d_qnx, d_qny, d_qnz, nq, radius,
-              d_out);
+  pcurv_rule({d_sx, d_sy, d_sz}, {d_snx, d_sny, d_snz}, n_surface, {d_qx, d_qy, d_qz}, {d_qnx, d_qny, d_qnz}, nq,
+             radius, d_out);
   pfx::pcurv_dev(ctx, d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, d_qnx, d_qny, d_qnz, nq,
                  radius, d_out);
   PFX_API_END(ctx)
@@ -909,27 +914,22 @@ pfx_status pfx_principal_curvatures(pfx_ctx* ctx, const float* sx, const float* 
                                     const float* qny, const float* qnz, int64_t nq, double radius, float* out) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  pcurv_check(sx, sy, sz, snx, sny, snz, n_surface, qx, qy, qz, qnx, qny, qnz, nq, radius, out);
-  if (nq) {
+  pcurv_rule({sx, sy, sz}, {snx, sny, snz}, n_surface, {qx, qy, qz}, {qnx, qny, qnz}, nq, radius, out);
+  if (nq) {  // (without queries nothing is staged, run or resolved)
     const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), n = stage3(ctx, "in_n", snx, sny, snz, n_surface);
     const Dev3 q = stage3(ctx, "in_q", qx, qy, qz, nq), a = stage3(ctx, "in_qn", qnx, qny, qnz, nq);
     float* dout = ctx->buf("out_pcurv").as<float>(nq * 5 + 1);
     pfx::pcurv_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, n_surface, q.x, q.y, q.z, a.x, a.y, a.z, nq, radius, dout);
-    rows_out(ctx, out, dout, nq, 5);
-    PFX_HIP(hipStreamSynchronize(ctx->stream));
-    pfx::reports_resolve(ctx, pfx::kRepMoments, pfx::kRepPcurv);  // the host API reports at once
+    finish_host(ctx, nq, {{out, dout, 5}}, pfx::kRepMoments, pfx::kRepPcurv);
   }
   PFX_API_END(ctx)
 }
 
-// every check that precedes a launch (host and device entry points alike)
-static void sc_check(const char* what, const float* sx, const float* sy, const float* sz, bool normals_ok,
-                     int64_t n_surface, const float* qx, const float* qy, const float* qz, bool frames_ok,
-                     int64_t nq, double radius, double min_radius, double density_radius, const float* desc,
-                     const float* rf) {
-  if (n_surface < 0 || nq < 0 || (nq && (!desc || !rf || !qx || !qy || !qz || !frames_ok)) ||
-      (n_surface && (!sx || !sy || !sz || !normals_ok)))
-    throw Error(PFX_ERR_INVALID, std::string(what) + ": invalid arguments");
+// Both shape contexts' rule.  `normals_set`: the 3DSC needs the surface normals, the USC has none;
+// `frames_set`: the USC needs the frames, the 3DSC has none.
+static void sc_rule(const char* what, In3 s, bool normals_set, int64_t n_surface, In3 q, bool frames_set, int64_t nq,
+                    double radius, double min_radius, double density_radius, const float* desc, const float* rf) {
+  args_rule(what, n_surface, all_set(s) && normals_set, nq, all_set(q, desc, rf) && frames_set);
   if (!(radius > 0.0) || !(min_radius > 0.0) || !(density_radius > 0.0))
     throw Error(PFX_ERR_INVALID, std::string(what) + ": every radius must be > 0");
   if (radius < min_radius)  // PCL's initCompute refuses this
@@ -943,8 +943,8 @@ pfx_status pfx_shape_context_dev(pfx_ctx* ctx, const float* d_sx, const float* d
                                  const float* d_rnd, float* d_desc, float* d_rf) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  sc_check("shape_context", d_sx, d_sy, d_sz, d_snx && d_sny && d_snz, n_surface, d_qx, d_qy, d_qz, true, nq,
-           radius, min_radius, point_density_radius, d_desc, d_rf);
+  sc_rule("shape_context", {d_sx, d_sy, d_sz}, all_set(d_snx, d_sny, d_snz), n_surface, {d_qx, d_qy, d_qz}, true, nq,
+          radius, min_radius, point_density_radius, d_desc, d_rf);
   pfx::sc_dev(ctx, d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, nullptr, nq, radius,
               min_radius, point_density_radius, d_rnd, d_desc, d_rf);
   PFX_API_END(ctx)
@@ -956,8 +956,8 @@ pfx_status pfx_shape_context(pfx_ctx* ctx, const float* sx, const float* sy, con
                              double point_density_radius, const float* rnd, float* desc, float* rf) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  sc_check("shape_context", sx, sy, sz, snx && sny && snz, n_surface, qx, qy, qz, true, nq, radius, min_radius,
-           point_density_radius, desc, rf);
+  sc_rule("shape_context", {sx, sy, sz}, all_set(snx, sny, snz), n_surface, {qx, qy, qz}, true, nq, radius,
+          min_radius, point_density_radius, desc, rf);
   const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), n = stage3(ctx, "in_n", snx, sny, snz, n_surface);
   const Dev3 q = stage3(ctx, "in_q", qx, qy, qz, nq);
   float* drnd = rnd ? stage_in(ctx, "in_sc_rnd", rnd, 3 * nq) : nullptr;
@@ -965,10 +965,7 @@ pfx_status pfx_shape_context(pfx_ctx* ctx, const float* sx, const float* sy, con
   float* drf = ctx->buf("out_sc_rf").as<float>(nq * 9 + 1);
   pfx::sc_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, n_surface, q.x, q.y, q.z, nullptr, nq, radius, min_radius,
               point_density_radius, drnd, ddesc, drf);
-  rows_out(ctx, desc, ddesc, nq, 1980);
-  rows_out(ctx, rf, drf, nq, 9);
-  PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::reports_resolve(ctx, pfx::kRepSc, pfx::kRepLrf);  // the host API reports at once
+  finish_host(ctx, nq, {{desc, ddesc, 1980}, {rf, drf, 9}}, pfx::kRepSc, pfx::kRepLrf);
   PFX_API_END(ctx)
 }
 
@@ -978,8 +975,8 @@ pfx_status pfx_usc_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const
                        float* d_rf) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  sc_check("usc", d_sx, d_sy, d_sz, true, n_surface, d_qx, d_qy, d_qz, d_frames != nullptr, nq, radius, min_radius,
-           point_density_radius, d_desc, d_rf);
+  sc_rule("usc", {d_sx, d_sy, d_sz}, true, n_surface, {d_qx, d_qy, d_qz}, all_set(d_frames), nq, radius, min_radius,
+          point_density_radius, d_desc, d_rf);
   pfx::sc_dev(ctx, d_sx, d_sy, d_sz, nullptr, nullptr, nullptr, n_surface, d_qx, d_qy, d_qz, d_frames, nq, radius,
               min_radius, point_density_radius, nullptr, d_desc, d_rf);
   PFX_API_END(ctx)
@@ -990,8 +987,8 @@ pfx_status pfx_usc(pfx_ctx* ctx, const float* sx, const float* sy, const float* 
                    double radius, double min_radius, double point_density_radius, float* desc, float* rf) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  sc_check("usc", sx, sy, sz, true, n_surface, qx, qy, qz, frames != nullptr, nq, radius, min_radius,
-           point_density_radius, desc, rf);
+  sc_rule("usc", {sx, sy, sz}, true, n_surface, {qx, qy, qz}, all_set(frames), nq, radius, min_radius,
+          point_density_radius, desc, rf);
   const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), q = stage3(ctx, "in_q", qx, qy, qz, nq);
   float* dfr = stage_in(ctx, "in_sc_frames", frames, 9 * nq);
   float* ddesc = ctx->buf("out_sc").as<float>(nq * 1980 + 1);
@@ -1000,18 +997,12 @@ pfx_status pfx_usc(pfx_ctx* ctx, const float* sx, const float* sy, const float* 
   if (nq)
     pfx::sc_dev(ctx, s.x, s.y, s.z, nullptr, nullptr, nullptr, n_surface, q.x, q.y, q.z, dfr, nq, radius, min_radius,
                 point_density_radius, nullptr, ddesc, drf);
-  rows_out(ctx, desc, ddesc, nq, 1980);
-  rows_out(ctx, rf, drf, nq, 9);
-  PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::reports_resolve(ctx, pfx::kRepSc, pfx::kRepLrf);  // the host API reports at once
+  finish_host(ctx, nq, {{desc, ddesc, 1980}, {rf, drf, 9}}, pfx::kRepSc, pfx::kRepLrf);
   PFX_API_END(ctx)
 }
 
-static void lrf_check(const float* sx, const float* sy, const float* sz, int64_t n_surface, const float* qx,
-                      const float* qy, const float* qz, int64_t nq, double radius, const float* rf) {
-  if (n_surface < 0 || nq < 0 || !(radius > 0.0) || (nq && (!rf || !qx || !qy || !qz)) ||
-      (n_surface && (!sx || !sy || !sz)))
-    throw Error(PFX_ERR_INVALID, "shot_lrf: invalid arguments");
+static void lrf_rule(In3 s, int64_t n_surface, In3 q, int64_t nq, double radius, const float* rf) {
+  args_rule("shot_lrf", n_surface, all_set(s), nq, all_set(q, rf), radius > 0.0);
 }
 
 pfx_status pfx_shot_lrf_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
@@ -1019,7 +1010,7 @@ pfx_status pfx_shot_lrf_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, 
                             double radius, float* d_rf) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  lrf_check(d_sx, d_sy, d_sz, n_surface, d_qx, d_qy, d_qz, nq, radius, d_rf);
+  lrf_rule({d_sx, d_sy, d_sz}, n_surface, {d_qx, d_qy, d_qz}, nq, radius, d_rf);
   pfx::shot_lrf_dev(ctx, d_sx, d_sy, d_sz, n_surface, d_qx, d_qy, d_qz, nq, radius, d_rf);
   PFX_API_END(ctx)
 }
@@ -1028,13 +1019,11 @@ pfx_status pfx_shot_lrf(pfx_ctx* ctx, const float* sx, const float* sy, const fl
                         const float* qx, const float* qy, const float* qz, int64_t nq, double radius, float* rf) {
   PFX_API_BEGIN
   check_ctx(ctx);
-  lrf_check(sx, sy, sz, n_surface, qx, qy, qz, nq, radius, rf);
+  lrf_rule({sx, sy, sz}, n_surface, {qx, qy, qz}, nq, radius, rf);
   const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), q = stage3(ctx, "in_q", qx, qy, qz, nq);
   float* drf = ctx->buf("out_sc_rf").as<float>(nq * 9 + 1);
   pfx::shot_lrf_dev(ctx, s.x, s.y, s.z, n_surface, q.x, q.y, q.z, nq, radius, drf);
-  rows_out(ctx, rf, drf, nq, 9);
-  PFX_HIP(hipStreamSynchronize(ctx->stream));
-  pfx::reports_resolve(ctx, pfx::kRepSc, pfx::kRepLrf);  // the host API reports at once
+  finish_host(ctx, nq, {{rf, drf, 9}}, pfx::kRepSc, pfx::kRepLrf);
   PFX_API_END(ctx)
 }
 
