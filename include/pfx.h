@@ -42,6 +42,8 @@
  *                          (features.h:175-196, evaluation.cpp:554-572)
  *   pfx_principal_curvatures* <- PrincipalCurvaturesEstimation<PointXYZRGB,Normal,
  *                          PrincipalCurvatures>::compute (features.h:175-196, evaluation.cpp:696-715)
+ *   pfx_board_lrf*      <- BOARDLocalReferenceFrameEstimation<PointXYZRGB,Normal,ReferenceFrame>
+ *                          ::compute (features.h:175-196, evaluation.cpp:372-393)
  *   pfx_range_image_planar* <- RangeImagePlanar::createFromPointCloudWithFixedSize
  *                          (keypoints.h:212-216, tools.h:61-77)
  *   pfx_narf_keypoints* <- RangeImageBorderExtractor + NarfKeypoint::compute
@@ -645,6 +647,62 @@ pfx_status pfx_principal_curvatures_dev(pfx_ctx* ctx, const float* d_sx, const f
                                         int64_t n_surface, const float* d_qx, const float* d_qy,
                                         const float* d_qz, const float* d_qnx, const float* d_qny,
                                         const float* d_qnz, int64_t nq, double radius, float* d_out);
+
+/* ---- BOARD local reference frames: BOARDLocalReferenceFrameEstimation<PointXYZRGB, Normal,
+ *      ReferenceFrame> (evaluation.cpp:372-393) ---------------------------------------------- */
+/* PCL's setters.  tangent_radius (0: unset, PCL's default and the reference's) and margin_thresh
+ * (0.85) must be finite and >= 0.  find_holes: only 0 is supported (PFX_ERR_UNSUPPORTED otherwise:
+ * PCL then seeds its angular bins from rand(), whose sequence runs on from one keypoint to the
+ * next).  check_margin_array_size (24), hole_size_prob_thresh (0.2) and steep_thresh (0.1) matter
+ * only with find_holes and are carried unused.  pfx_board_params_default fills 0, 0.85, 0, 24,
+ * 0.2, 0.1. */
+typedef struct pfx_board_params {
+  float tangent_radius;
+  float margin_thresh;
+  int32_t find_holes;
+  int32_t check_margin_array_size;
+  float hole_size_prob_thresh;
+  float steep_thresh;
+} pfx_board_params;
+void pfx_board_params_default(pfx_board_params* p);
+/* rf: nq x 9 floats, the x, y and z axis of every row (pfx_shot_lrf's layout).  DESIGN.md "BOARD:
+ * the contract" states every operation; the CPU restatement of that text is the truth the kernel
+ * is tested against (parity with PCL itself is unpinned, and the z axis is this project's
+ * definition: PCL's float SVD cannot be restated bit for bit).  All in float32 left to right
+ * without FMA contraction unless said otherwise; neighbours in FLANN order, strict
+ * d^2 < (float)(radius^2).
+ *   support    the radius neighbours of query i; fewer than 6: a NaN row.
+ *   z          centroid = the sequential sums of the neighbours' xyz, each / float(k); the six
+ *              sums of (s - c)(s - c)^T in double, in neighbour order; z = the eigenvector of the
+ *              smallest eigenvalue (Eigen 3.2's SelfAdjointEigenSolver<Matrix3d>, as for SHOT's
+ *              frames), cast to float; negated when its dot product with the normalised sum of
+ *              the neighbours' normals is < 0 (a NaN sum never flips).
+ *   tangent    with tangent_radius != 0 and != radius, the neighbours at tangent_radius replace
+ *              the support from here on.  margin2 = (margin_thresh margin_thresh) (tangent_radius
+ *              tangent_radius): 0 with the tangent radius unset, so that every neighbour with
+ *              d^2 > 0 is "on the margin" (PCL 1.7's behaviour, kept).
+ *   x          the neighbour with d^2 > margin2 whose normal has the smallest z . n, the first
+ *              strict minimum in neighbour order (a NaN never wins); when no neighbour has
+ *              d^2 > margin2, the same over all of them; nothing chosen: a NaN row.  With b that
+ *              neighbour and p the query: x = (b - (z . (b - p)) z) - p, divided by its norm;
+ *              y = z cross x.  b on the line through p along z: x and y NaN, z finite.
+ * Every NaN is written as 0x7fc00000.  A null required pointer (params included), a negative
+ * size, radius <= 0, a negative or non-finite tangent_radius or margin_thresh: PFX_ERR_INVALID
+ * before anything is copied or launched.  nq == 0 is a no-op; n_surface == 0 fills rf with NaN.
+ * The keys of a query are gathered once at max(radius, tangent_radius): more than 16384 of them
+ * is PFX_ERR_CAPACITY.  Statistics: "board_neighbors" (sum of the gathered k), "board_kmax",
+ * "board_queued" (rows with more than "board_cap_small" keys, which take the second pass);
+ * "board_cap_small" can be read from a new ctx. */
+pfx_status pfx_board_lrf(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
+                         const float* sny, const float* snz, int64_t n_surface, const float* qx, const float* qy,
+                         const float* qz, int64_t nq, double radius, const pfx_board_params* params, float* rf);
+/* Device pointers, stream-ordered on the ctx stream, no host synchronisation (the surface grid's
+ * bounds are read back when it was not prepared ahead); late errors and statistics as
+ * pfx_spin_image_dev. */
+pfx_status pfx_board_lrf_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                             const float* d_snx, const float* d_sny, const float* d_snz, int64_t n_surface,
+                             const float* d_qx, const float* d_qy, const float* d_qz, int64_t nq, double radius,
+                             const pfx_board_params* params, float* d_rf);
 
 /* ---- range image + NARF keypoints ---------------------------------------------------- */
 /* out_points: width*height x 4 floats {x, y, z, range} (PointWithRange); unobserved pixels

@@ -334,6 +334,10 @@ class Feature {
   // Feature::compute: initCompute -> computeFeature -> deinitCompute
   void compute(PointCloudOut& output) {
     output.clear();
+    if (k_ != 0 && !k_search_error_.empty()) {
+      PCL_ERROR("%s\n", k_search_error_.c_str());
+      return;
+    }
     if (!input_ || input_->empty() || k_ != 0 || !(search_radius_ > 0.0)) {
       PCL_ERROR("[pcl::%s::compute] initCompute failed (needs an input cloud and a radius; "
                 "k-NN search is not on the accelerated path)\n", name_.c_str());
@@ -356,6 +360,7 @@ class Feature {
     return false;
   }
   std::string name_ = "Feature";
+  std::string k_search_error_;  // a class whose PCL original refuses a k-search in its own words sets them
   PointCloudInConstPtr input_, surface_;
   KdTreePtr tree_;
   double search_radius_ = 0.0;
@@ -905,6 +910,53 @@ class SHOTLocalReferenceFrameEstimation : public Feature<PointInT, PointOutT> {
   }
 };
 
+// BOARDLocalReferenceFrameEstimation<In, Normal, ReferenceFrame> (evaluation.cpp:372-393): the frames
+// of pfx_board_lrf, a NaN frame where fewer than six neighbours define it or no normal qualifies.
+// Hole analysis (setFindHoles(true)) is not on the accelerated path: PCL seeds it from rand(), and
+// compute() fails; its three parameters are kept for the getters.
+template <typename PointInT, typename PointNT, typename PointOutT = ReferenceFrame>
+class BOARDLocalReferenceFrameEstimation : public FeatureFromNormals<PointInT, PointNT, PointOutT> {
+ public:
+  typedef std::shared_ptr<BOARDLocalReferenceFrameEstimation<PointInT, PointNT, PointOutT> > Ptr;
+  typedef std::shared_ptr<const BOARDLocalReferenceFrameEstimation<PointInT, PointNT, PointOutT> > ConstPtr;
+  BOARDLocalReferenceFrameEstimation() {
+    this->name_ = "BOARDLocalReferenceFrameEstimation";
+    // (PCL's computeFeature refuses a k-search itself, with these words)
+    this->k_search_error_ = "[pcl::BOARDLocalReferenceFrameEstimation::computeFeature] Error! Search method set to "
+                            "k-neighborhood. Call setKSearch(0) and setRadiusSearch( radius ) to use this class.";
+    pfx_board_params_default(&prm_);
+  }
+  void setTangentRadius(float radius) { prm_.tangent_radius = radius; }
+  float getTangentRadius() const { return prm_.tangent_radius; }
+  void setFindHoles(bool find_holes) { prm_.find_holes = find_holes ? 1 : 0; }
+  bool getFindHoles() const { return prm_.find_holes != 0; }
+  void setMarginThresh(float margin_thresh) { prm_.margin_thresh = margin_thresh; }
+  float getMarginThresh() const { return prm_.margin_thresh; }
+  void setCheckMarginArraySize(int size) { prm_.check_margin_array_size = size; }
+  int getCheckMarginArraySize() const { return prm_.check_margin_array_size; }
+  void setHoleSizeProbThresh(float prob_thresh) { prm_.hole_size_prob_thresh = prob_thresh; }
+  float getHoleSizeProbThresh() const { return prm_.hole_size_prob_thresh; }
+  void setSteepThresh(float steep_thresh) { prm_.steep_thresh = steep_thresh; }
+  float getSteepThresh() const { return prm_.steep_thresh; }
+
+ protected:
+  void computeFeature(PointCloud<PointOutT>& out) override {
+    if (!this->normals_match("the input normals are missing or do not match the search surface")) return;
+    const detail::SoA s = detail::soa_xyz(this->surface()), q = detail::soa_xyz(*this->input_);
+    const detail::SoA nrm = detail::soa_normals(*this->normals_);
+    std::vector<float> rf(q.size() * 9);
+    if (!detail::ok(pfx_board_lrf(detail::context(), s.x.data(), s.y.data(), s.z.data(), nrm.x.data(), nrm.y.data(),
+                                  nrm.z.data(), s.n(), q.x.data(), q.y.data(), q.z.data(), q.n(),
+                                  this->search_radius_, &prm_, rf.data()),
+                    "BOARDLocalReferenceFrameEstimation"))
+      return;
+    // (a ReferenceFrame is its x, y and z axes in a row, as the C-ABI's nine floats are; a computed
+    // row can have NaN x and y axes beside a finite z)
+    detail::write_rows<9>(out, q.size(), detail::NanRule::kAnyFloat, rf);
+  }
+  pfx_board_params prm_;
+};
+
 // UniqueShapeContext<In, ShapeContext1980, ReferenceFrame>.  Without input frames it computes them
 // with SHOTLocalReferenceFrameEstimation at the local radius (PCL's default: 2.5) over the search
 // surface.  That frame search has SHOT's capacity, 16,384 neighbours: on a cloud where the local
@@ -1319,6 +1371,8 @@ template <> struct DescriptorLayout<MomentInvariants> { static constexpr int dim
 // (DefaultPointRepresentation caps a point type it does not know at its first three floats: the
 // principal direction alone is compared)
 template <> struct DescriptorLayout<PrincipalCurvatures> { static constexpr int dim = 3, stride = 5; };
+// (the same rule for the nine floats of a ReferenceFrame: the x axis alone is compared)
+template <> struct DescriptorLayout<ReferenceFrame> { static constexpr int dim = 3, stride = 9; };
 }  // namespace detail
 
 // KdTreeFLANN<FeatureT> with nearestKSearch(k = 1), as the reference uses it (features.h:258-272):

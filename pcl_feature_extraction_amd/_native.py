@@ -87,6 +87,18 @@ class SpinParams(ctypes.Structure):
     ]
 
 
+class BoardParams(ctypes.Structure):
+    """pfx_board_params (BOARDLocalReferenceFrameEstimation's setters)."""
+    _fields_ = [
+        ("tangent_radius", ctypes.c_float),
+        ("margin_thresh", ctypes.c_float),
+        ("find_holes", ctypes.c_int32),
+        ("check_margin_array_size", ctypes.c_int32),
+        ("hole_size_prob_thresh", ctypes.c_float),
+        ("steep_thresh", ctypes.c_float),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "pfx_narf_params_default": (None, [ctypes.POINTER(NarfParams)]),
@@ -163,6 +175,11 @@ _SIGS = {
                                          c_vp, c_vp, c_i64, c_dbl, c_vp]),
     "pfx_principal_curvatures_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                              c_vp, c_vp, c_i64, c_dbl, c_vp]),
+    "pfx_board_params_default": (None, [ctypes.POINTER(BoardParams)]),
+    "pfx_board_lrf": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
+                              ctypes.POINTER(BoardParams), c_vp]),
+    "pfx_board_lrf_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
+                                  ctypes.POINTER(BoardParams), c_vp]),
     "pfx_shape_context": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
                                   c_dbl, c_dbl, c_vp, c_vp, c_vp]),
     "pfx_shape_context_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
@@ -228,14 +245,15 @@ _SIGS = {
 
 # entry points an older library loaded through PFX_LIB (A/B runs against a previous build) may lack:
 # test hooks, ICP, spin images, intensity gradients, RIFT, intensity spin images, the shape contexts,
-# moment invariants and principal curvatures (calling a missing one raises AttributeError there)
+# moment invariants, principal curvatures and BOARD frames (calling a missing one raises AttributeError there)
 _OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_icp_dev",
                    "pfx_spin_params_default", "pfx_spin_image", "pfx_spin_image_dev",
                    "pfx_intensity_gradient", "pfx_intensity_gradient_dev", "pfx_rift", "pfx_rift_dev",
                    "pfx_intensity_spin", "pfx_intensity_spin_dev",
                    "pfx_shape_context", "pfx_shape_context_dev", "pfx_usc", "pfx_usc_dev", "pfx_shot_lrf",
                    "pfx_shot_lrf_dev", "pfx_rng_uniform01", "pfx_moment_invariants", "pfx_moment_invariants_dev",
-                   "pfx_principal_curvatures", "pfx_principal_curvatures_dev"}
+                   "pfx_principal_curvatures", "pfx_principal_curvatures_dev",
+                   "pfx_board_params_default", "pfx_board_lrf", "pfx_board_lrf_dev"}
 
 _lib = None
 

@@ -75,6 +75,15 @@ def spin_params(image_width=8, support_angle_cos=0.0, min_pts_neighb=0, radial=0
     return p
 
 
+def board_params(tangent_radius=0.0, margin_thresh=0.85, find_holes=False) -> N.BoardParams:
+    """pfx_board_params; the defaults are PCL's (pfx_board_params_default).  The three hole parameters
+    keep their defaults: they matter only with find_holes, which is not supported."""
+    p = N.BoardParams()
+    N.lib().pfx_board_params_default(ctypes.byref(p))
+    p.tangent_radius, p.margin_thresh, p.find_holes = float(tangent_radius), float(margin_thresh), int(bool(find_holes))
+    return p
+
+
 def rgb_to_intensity(rgb) -> np.ndarray:
     """pcl::PointXYZRGBtoXYZI on packed 0x00RRGGBB words: (0.299f * r + 0.587f * g) + 0.114f * b,
     every step in float32.  Input preparation for Context.intensity_gradient, not a feature."""
@@ -395,6 +404,22 @@ class Context:
                                            _ptr(qz), len(qx), float(r), _ptr(rf)))
         return rf
 
+    def board_lrf(self, sx, sy, sz, snx, sny, snz, qx, qy, qz, r, tangent_radius=0.0, margin_thresh=0.85,
+                  find_holes=False):
+        """BOARDLocalReferenceFrameEstimation (pfx_board_lrf): (nq, 9) float32, the x, y and z axis of
+        every row (shot_lrf's layout); (snx, sny, snz) are the surface normals.  A NaN row for a query
+        with fewer than six neighbours or without a usable normal around it.  find_holes=True is
+        PFX_ERR_UNSUPPORTED."""
+        sx, sy, sz, snx, sny, snz, qx, qy, qz = map(_f32, (sx, sy, sz, snx, sny, snz, qx, qy, qz))
+        if len(snx) != len(sx):
+            raise ValueError("board_lrf: one normal per surface point")
+        rf = np.empty((len(qx), 9), dtype=np.float32)
+        p = board_params(tangent_radius, margin_thresh, find_holes)
+        self._check(self._lib.pfx_board_lrf(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(snx), _ptr(sny), _ptr(snz),
+                                            len(sx), _ptr(qx), _ptr(qy), _ptr(qz), len(qx), float(r), ctypes.byref(p),
+                                            _ptr(rf)))
+        return rf
+
     def range_image_planar(self, x, y, z, cam=None):
         cam = cam or camera()
         x, y, z = map(_f32, (x, y, z))
@@ -631,6 +656,15 @@ class Context:
         reported by the next synchronize()."""
         self._check(self._lib.pfx_shot_lrf_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), sx.numel(), _ptr(qx), _ptr(qy),
                                                _ptr(qz), qx.numel(), float(r), _ptr(rf)))
+
+    def board_lrf_dev(self, sx, sy, sz, snx, sny, snz, qx, qy, qz, r, rf, tangent_radius=0.0, margin_thresh=0.85,
+                      find_holes=False):
+        """pfx_board_lrf_dev: rf is an (nq, 9) float32 device tensor; no host synchronisation (a
+        neighbourhood beyond capacity is reported by the next synchronize())."""
+        p = board_params(tangent_radius, margin_thresh, find_holes)
+        self._check(self._lib.pfx_board_lrf_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(snx), _ptr(sny), _ptr(snz),
+                                                sx.numel(), _ptr(qx), _ptr(qy), _ptr(qz), qx.numel(), float(r),
+                                                ctypes.byref(p), _ptr(rf)))
 
     def narf_keypoints_dev(self, x, y, z, params=None, cam=None, cap=1 << 20):
         cam = cam or camera()

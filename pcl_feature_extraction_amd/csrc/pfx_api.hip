@@ -1,5 +1,6 @@
 // pfx_api.hip -- the extern "C" boundary (include/pfx.h).  Host-pointer entry points stage
 // through ctx-owned device buffers and call the stream-ordered *_dev implementations.
+#include <cmath>
 #include <cstring>
 
 #include "pfx_internal.h"
@@ -190,6 +191,7 @@ pfx_status pfx_ctx_create(int device, pfx_ctx** out) {
     ctx->stats["ispin_tile"] = pfx::ispin_tile(20);  // of the default 4 x 5 image
     ctx->stats["sc_cap_small"] = pfx::sc_cap_small();
     ctx->stats["moments_cap_small"] = pfx::moments_cap_small();
+    ctx->stats["board_cap_small"] = pfx::board_cap_small();
     // grid builds by builder (pfx_grid.hip), and speculative counting builds that met a fat cell
     for (const char* s : {"grid_count_builds", "grid_sort_builds", "grid_hinted_sort_builds", "grid_fat_fallbacks"})
       ctx->stats[s] = 0;
@@ -921,6 +923,55 @@ pfx_status pfx_principal_curvatures(pfx_ctx* ctx, const float* sx, const float* 
     float* dout = ctx->buf("out_pcurv").as<float>(nq * 5 + 1);
     pfx::pcurv_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, n_surface, q.x, q.y, q.z, a.x, a.y, a.z, nq, radius, dout);
     finish_host(ctx, nq, {{out, dout, 5}}, pfx::kRepMoments, pfx::kRepPcurv);
+  }
+  PFX_API_END(ctx)
+}
+
+void pfx_board_params_default(pfx_board_params* p) {
+  if (!p) return;
+  p->tangent_radius = 0.0f;
+  p->margin_thresh = 0.85f;
+  p->find_holes = 0;
+  p->check_margin_array_size = 24;
+  p->hole_size_prob_thresh = 0.2f;
+  p->steep_thresh = 0.1f;
+}
+
+static void board_rule(In3 s, In3 n, int64_t n_surface, In3 q, int64_t nq, double radius, const pfx_board_params* p,
+                       const float* rf) {
+  args_rule("board_lrf", n_surface, all_set(s, n), nq, all_set(q, rf), p && radius > 0.0);
+  if (!(p->tangent_radius >= 0.0f) || std::isinf(p->tangent_radius))
+    throw Error(PFX_ERR_INVALID, "board_lrf: tangent_radius must be finite and >= 0");
+  if (!(p->margin_thresh >= 0.0f) || std::isinf(p->margin_thresh))
+    throw Error(PFX_ERR_INVALID, "board_lrf: margin_thresh must be finite and >= 0");
+  if (p->find_holes != 0)
+    throw Error(PFX_ERR_UNSUPPORTED, "board_lrf: find_holes is not supported (PCL seeds its angular bins from "
+                                     "rand(), so the frames depend on the process's history)");
+}
+
+pfx_status pfx_board_lrf_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                             const float* d_snx, const float* d_sny, const float* d_snz, int64_t n_surface,
+                             const float* d_qx, const float* d_qy, const float* d_qz, int64_t nq, double radius,
+                             const pfx_board_params* params, float* d_rf) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  board_rule({d_sx, d_sy, d_sz}, {d_snx, d_sny, d_snz}, n_surface, {d_qx, d_qy, d_qz}, nq, radius, params, d_rf);
+  pfx::board_dev(ctx, d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, n_surface, d_qx, d_qy, d_qz, nq, radius, *params, d_rf);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_board_lrf(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
+                         const float* sny, const float* snz, int64_t n_surface, const float* qx, const float* qy,
+                         const float* qz, int64_t nq, double radius, const pfx_board_params* params, float* rf) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  board_rule({sx, sy, sz}, {snx, sny, snz}, n_surface, {qx, qy, qz}, nq, radius, params, rf);
+  if (nq) {  // (without queries nothing is staged, run or resolved)
+    const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), n = stage3(ctx, "in_n", snx, sny, snz, n_surface);
+    const Dev3 q = stage3(ctx, "in_q", qx, qy, qz, nq);
+    float* drf = ctx->buf("out_board").as<float>(nq * 9 + 1);
+    pfx::board_dev(ctx, s.x, s.y, s.z, n.x, n.y, n.z, n_surface, q.x, q.y, q.z, nq, radius, *params, drf);
+    finish_host(ctx, nq, {{rf, drf, 9}}, pfx::kRepBoard, pfx::kRepBoard);
   }
   PFX_API_END(ctx)
 }

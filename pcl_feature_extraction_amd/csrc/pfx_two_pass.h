@@ -1,6 +1,7 @@
 // pfx_two_pass.h -- the frame of the descriptors that give a query one 256-thread workgroup and hold
 // its FLANN-ordered neighbour keys in LDS (spin images, intensity gradient, RIFT, intensity spin images,
-// shape contexts, moments and curvatures, SHOT's frames alone).  DESIGN.md "The descriptors' common frame".
+// shape contexts, moments and curvatures, SHOT's frames alone, BOARD's frames).  DESIGN.md "The descriptors'
+// common frame".
 //
 // Two passes: every query with kTwoPassCapSmall keys and the bucketed sort; a query with more
 // neighbours is queued on the device for the second pass with kTwoPassCap keys and the bitonic sort
