@@ -44,6 +44,8 @@
  *                          PrincipalCurvatures>::compute (features.h:175-196, evaluation.cpp:696-715)
  *   pfx_board_lrf*      <- BOARDLocalReferenceFrameEstimation<PointXYZRGB,Normal,ReferenceFrame>
  *                          ::compute (features.h:175-196, evaluation.cpp:372-393)
+ *   pfx_boundary*       <- BoundaryEstimation<PointXYZRGB,Normal,Boundary>::compute
+ *                          (features.h:175-196, evaluation.cpp:394-415)
  *   pfx_range_image_planar* <- RangeImagePlanar::createFromPointCloudWithFixedSize
  *                          (keypoints.h:212-216, tools.h:61-77)
  *   pfx_narf_keypoints* <- RangeImageBorderExtractor + NarfKeypoint::compute
@@ -703,6 +705,41 @@ pfx_status pfx_board_lrf_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy,
                              const float* d_snx, const float* d_sny, const float* d_snz, int64_t n_surface,
                              const float* d_qx, const float* d_qy, const float* d_qz, int64_t nq, double radius,
                              const pfx_board_params* params, float* d_rf);
+
+/* ---- boundary points: BoundaryEstimation<PointXYZRGB, Normal, Boundary>
+ *      (evaluation.cpp:394-415) ------------------------------------------------------------ */
+/* out: nq bytes, 1 for a query on a boundary of the surface (a scan edge, a hole's rim), 0 for one
+ * that is not, PFX_BOUNDARY_NO_NEIGHBORS for one without a neighbour.  (qnx, qny, qnz) are the
+ * normals of the QUERIES, one per query; no surface normal is read.  DESIGN.md "Boundary: the
+ * contract" states every operation; the CPU restatement of that text is the truth the kernel is
+ * tested against (parity with PCL itself is unpinned).  All in float32 left to right without FMA
+ * contraction; the neighbours are the set with d^2 < (float)(radius^2), k of them, in any order.
+ *   k == 0     PFX_BOUNDARY_NO_NEIGHBORS; k < 3: 0.
+ *   axes       v = Eigen's unitOrthogonal of (n, 0), u = n cross v (PCL's
+ *              getCoordinateSystemOnPlane); a non-finite component of either (a NaN, an infinite or
+ *              a zero normal): 0.
+ *   angles     atan2f(v . d, u . d) for every neighbour with d = p - q != 0 (glibc's routine);
+ *              none: 0.  A NaN angle (dot products that overflow): 0.
+ *   gap test   1 when two angles adjacent in ascending order differ by more than angle_threshold,
+ *              or (2 pi - the largest) + the smallest does; else 0.
+ * angle_threshold (PCL's default: pi / 2) below (float)(pi / 64) is PFX_ERR_UNSUPPORTED: the kernel
+ * does not sort; it compares the angles across 256 bins and never within one, which is exact only
+ * for a threshold of at least two bin widths.  A NaN angle_threshold, a null required pointer, a
+ * negative size, radius <= 0: PFX_ERR_INVALID before anything is copied or launched.  nq == 0 is a
+ * no-op; n_surface == 0 fills out with PFX_BOUNDARY_NO_NEIGHBORS.  There is no capacity: a query
+ * may have any number of neighbours.  Statistics: "boundary_neighbors" (sum of k),
+ * "boundary_kmax", "boundary_flagged" (the number of 1s). */
+#define PFX_BOUNDARY_NO_NEIGHBORS 255
+pfx_status pfx_boundary(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t n_surface,
+                        const float* qx, const float* qy, const float* qz, const float* qnx, const float* qny,
+                        const float* qnz, int64_t nq, double radius, float angle_threshold, uint8_t* out);
+/* Device pointers, stream-ordered on the ctx stream, no host synchronisation (the surface grid's
+ * bounds are read back when it was not prepared ahead); nothing is reported late but the
+ * statistics, which the next synchronisation of the ctx brings. */
+pfx_status pfx_boundary_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz,
+                            int64_t n_surface, const float* d_qx, const float* d_qy, const float* d_qz,
+                            const float* d_qnx, const float* d_qny, const float* d_qnz, int64_t nq,
+                            double radius, float angle_threshold, uint8_t* d_out);
 
 /* ---- range image + NARF keypoints ---------------------------------------------------- */
 /* out_points: width*height x 4 floats {x, y, z, range} (PointWithRange); unobserved pixels

@@ -225,6 +225,9 @@ struct SHOT352 { float descriptor[352]; float rf[9]; };
 struct SHOT1344 { float descriptor[1344]; float rf[9]; };
 struct ShapeContext1980 { float descriptor[1980]; float rf[9]; };
 struct ReferenceFrame { float x_axis[3], y_axis[3], z_axis[3]; };
+// pcl::Boundary: one byte
+struct Boundary { uint8_t boundary_point = 0; };
+static_assert(sizeof(Boundary) == 1, "pcl::Boundary is one byte");
 
 // pcl::PCLException, as far as the facade throws it (SpinImageEstimation where PCL's throws)
 class PCLException : public std::runtime_error {
@@ -955,6 +958,48 @@ class BOARDLocalReferenceFrameEstimation : public FeatureFromNormals<PointInT, P
     detail::write_rows<9>(out, q.size(), detail::NanRule::kAnyFloat, rf);
   }
   pfx_board_params prm_;
+};
+
+// BoundaryEstimation<In, Normal, Boundary> (evaluation.cpp:394-415): the flags of pfx_boundary.
+// PCL 1.7's indexing: the normal of input point i is `normals_->points[(*indices_)[i]]`, that is
+// normals_[i], while the reference hands in one normal per point of the search *surface*; a
+// keypoint that is not surface point i gets surface point i's normal all the same.  Reproduced: the
+// facade passes normals[0 .. nq) as the queries' normals.  More input points than normals, which
+// PCL would read out of bounds, is an error here.
+// A row without a neighbour (PFX_BOUNDARY_NO_NEIGHBORS) is boundary_point = 0 and is_dense = false:
+// PCL assigns quiet_NaN() of uint8_t, which is 0.  There is no KdTreeFLANN<Boundary>: matching on the
+// flags is not on this path.
+template <typename PointInT, typename PointNT, typename PointOutT = Boundary>
+class BoundaryEstimation : public FeatureFromNormals<PointInT, PointNT, PointOutT> {
+ public:
+  typedef std::shared_ptr<BoundaryEstimation<PointInT, PointNT, PointOutT> > Ptr;
+  typedef std::shared_ptr<const BoundaryEstimation<PointInT, PointNT, PointOutT> > ConstPtr;
+  BoundaryEstimation() { this->name_ = "BoundaryEstimation"; }
+  void setAngleThreshold(float angle) { angle_threshold_ = angle; }
+  float getAngleThreshold() const { return angle_threshold_; }
+
+ protected:
+  void computeFeature(PointCloud<PointOutT>& out) override {
+    if (!this->normals_match("the input normals are missing or do not match the search surface")) return;
+    if (!this->input_within_surface()) return;  // row i reads normals_[i]
+    const detail::SoA s = detail::soa_xyz(this->surface()), q = detail::soa_xyz(*this->input_);
+    const detail::SoA nrm = detail::soa_normals(*this->normals_);
+    std::vector<uint8_t> flags(q.size());
+    // (the query normals are the first nq surface normals: the arrays' own prefixes)
+    if (!detail::ok(pfx_boundary(detail::context(), s.x.data(), s.y.data(), s.z.data(), s.n(), q.x.data(), q.y.data(),
+                                 q.z.data(), nrm.x.data(), nrm.y.data(), nrm.z.data(), q.n(), this->search_radius_,
+                                 angle_threshold_, flags.data()),
+                    "BoundaryEstimation"))
+      return;
+    out.resize(q.size());
+    out.is_dense = true;
+    for (size_t i = 0; i < q.size(); ++i) {
+      const bool none = flags[i] == PFX_BOUNDARY_NO_NEIGHBORS;
+      out.points[i].boundary_point = none ? 0 : flags[i];
+      if (none) out.is_dense = false;
+    }
+  }
+  float angle_threshold_ = static_cast<float>(M_PI) / 2.0f;
 };
 
 // UniqueShapeContext<In, ShapeContext1980, ReferenceFrame>.  Without input frames it computes them

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PFX_LIB") or os.path.join(_HERE, "libpfx.so")
 
 PFX_OK, PFX_ERR_INVALID, PFX_ERR_DEVICE, PFX_ERR_CAPACITY, PFX_ERR_UNSUPPORTED = 0, 1, 2, 3, 4
+BOUNDARY_NO_NEIGHBORS = 255   # PFX_BOUNDARY_NO_NEIGHBORS: a row of pfx_boundary without a neighbour
 _ERRNAMES = {1: "PFX_ERR_INVALID", 2: "PFX_ERR_DEVICE", 3: "PFX_ERR_CAPACITY", 4: "PFX_ERR_UNSUPPORTED"}
 
 c_f32p = ctypes.POINTER(ctypes.c_float)
@@ -180,6 +181,10 @@ _SIGS = {
                               ctypes.POINTER(BoardParams), c_vp]),
     "pfx_board_lrf_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
                                   ctypes.POINTER(BoardParams), c_vp]),
+    "pfx_boundary": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_dbl,
+                             ctypes.c_float, c_vp]),
+    "pfx_boundary_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_dbl,
+                                 ctypes.c_float, c_vp]),
     "pfx_shape_context": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
                                   c_dbl, c_dbl, c_vp, c_vp, c_vp]),
     "pfx_shape_context_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
@@ -245,7 +250,8 @@ _SIGS = {
 
 # entry points an older library loaded through PFX_LIB (A/B runs against a previous build) may lack:
 # test hooks, ICP, spin images, intensity gradients, RIFT, intensity spin images, the shape contexts,
-# moment invariants, principal curvatures and BOARD frames (calling a missing one raises AttributeError there)
+# moment invariants, principal curvatures, BOARD frames and boundary points (calling a missing one raises
+# AttributeError there)
 _OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_icp_dev",
                    "pfx_spin_params_default", "pfx_spin_image", "pfx_spin_image_dev",
                    "pfx_intensity_gradient", "pfx_intensity_gradient_dev", "pfx_rift", "pfx_rift_dev",
@@ -253,7 +259,8 @@ _OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_i
                    "pfx_shape_context", "pfx_shape_context_dev", "pfx_usc", "pfx_usc_dev", "pfx_shot_lrf",
                    "pfx_shot_lrf_dev", "pfx_rng_uniform01", "pfx_moment_invariants", "pfx_moment_invariants_dev",
                    "pfx_principal_curvatures", "pfx_principal_curvatures_dev",
-                   "pfx_board_params_default", "pfx_board_lrf", "pfx_board_lrf_dev"}
+                   "pfx_board_params_default", "pfx_board_lrf", "pfx_board_lrf_dev",
+                   "pfx_boundary", "pfx_boundary_dev"}
 
 _lib = None
 

@@ -6,6 +6,7 @@ CPU.  ``Context`` owns one ``pfx_ctx`` (one HIP stream) on one device.
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 
@@ -420,6 +421,20 @@ class Context:
                                             _ptr(rf)))
         return rf
 
+    def boundary(self, sx, sy, sz, qx, qy, qz, qnx, qny, qnz, r, angle_threshold=math.pi / 2):
+        """BoundaryEstimation (pfx_boundary): (nq,) uint8, 1 for a query on a boundary of the surface, 0
+        for one that is not, BOUNDARY_NO_NEIGHBORS for one without a neighbour.  (qnx, qny, qnz) are the
+        queries' normals, one per query.  Any number of neighbours; an angle_threshold below pi / 64 is
+        PFX_ERR_UNSUPPORTED."""
+        sx, sy, sz, qx, qy, qz, qnx, qny, qnz = map(_f32, (sx, sy, sz, qx, qy, qz, qnx, qny, qnz))
+        if len(qnx) != len(qx):
+            raise ValueError("boundary: one normal per query")
+        out = np.empty(len(qx), dtype=np.uint8)
+        self._check(self._lib.pfx_boundary(self.h, _ptr(sx), _ptr(sy), _ptr(sz), len(sx), _ptr(qx), _ptr(qy),
+                                           _ptr(qz), _ptr(qnx), _ptr(qny), _ptr(qnz), len(qx), float(r),
+                                           float(angle_threshold), _ptr(out)))
+        return out
+
     def range_image_planar(self, x, y, z, cam=None):
         cam = cam or camera()
         x, y, z = map(_f32, (x, y, z))
@@ -665,6 +680,13 @@ class Context:
         self._check(self._lib.pfx_board_lrf_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(snx), _ptr(sny), _ptr(snz),
                                                 sx.numel(), _ptr(qx), _ptr(qy), _ptr(qz), qx.numel(), float(r),
                                                 ctypes.byref(p), _ptr(rf)))
+
+    def boundary_dev(self, sx, sy, sz, qx, qy, qz, qnx, qny, qnz, r, out, angle_threshold=math.pi / 2):
+        """pfx_boundary_dev: out is an (nq,) uint8 device tensor; no host synchronisation (the statistics
+        come with the next synchronize(); nothing else is reported late)."""
+        self._check(self._lib.pfx_boundary_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), sx.numel(), _ptr(qx), _ptr(qy),
+                                               _ptr(qz), _ptr(qnx), _ptr(qny), _ptr(qnz), qx.numel(), float(r),
+                                               float(angle_threshold), _ptr(out)))
 
     def narf_keypoints_dev(self, x, y, z, params=None, cam=None, cap=1 << 20):
         cam = cam or camera()

@@ -976,6 +976,44 @@ pfx_status pfx_board_lrf(pfx_ctx* ctx, const float* sx, const float* sy, const f
   PFX_API_END(ctx)
 }
 
+static void boundary_rule(In3 s, int64_t n_surface, In3 q, In3 qn, int64_t nq, double radius, float angle_threshold,
+                          const uint8_t* out) {
+  args_rule("boundary", n_surface, all_set(s), nq, all_set(q, qn, out),
+            radius > 0.0 && !std::isnan(angle_threshold));
+  if (angle_threshold < (float)(M_PI / 64.0))
+    throw Error(PFX_ERR_UNSUPPORTED, "boundary: angle_threshold is below pi / 64 (the kernel compares the angles "
+                                     "across 256 bins and never within one: a gap below two bin widths could hide)");
+}
+
+pfx_status pfx_boundary_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz, int64_t n_surface,
+                            const float* d_qx, const float* d_qy, const float* d_qz, const float* d_qnx,
+                            const float* d_qny, const float* d_qnz, int64_t nq, double radius, float angle_threshold,
+                            uint8_t* d_out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  boundary_rule({d_sx, d_sy, d_sz}, n_surface, {d_qx, d_qy, d_qz}, {d_qnx, d_qny, d_qnz}, nq, radius, angle_threshold,
+                d_out);
+  pfx::boundary_dev(ctx, d_sx, d_sy, d_sz, n_surface, d_qx, d_qy, d_qz, d_qnx, d_qny, d_qnz, nq, radius,
+                    angle_threshold, d_out);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_boundary(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t n_surface,
+                        const float* qx, const float* qy, const float* qz, const float* qnx, const float* qny,
+                        const float* qnz, int64_t nq, double radius, float angle_threshold, uint8_t* out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  boundary_rule({sx, sy, sz}, n_surface, {qx, qy, qz}, {qnx, qny, qnz}, nq, radius, angle_threshold, out);
+  if (nq) {  // (without queries nothing is staged, run or resolved)
+    const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), q = stage3(ctx, "in_q", qx, qy, qz, nq);
+    const Dev3 a = stage3(ctx, "in_qn", qnx, qny, qnz, nq);
+    uint8_t* dout = ctx->buf("out_boundary").as<uint8_t>(nq + 1);
+    pfx::boundary_dev(ctx, s.x, s.y, s.z, n_surface, q.x, q.y, q.z, a.x, a.y, a.z, nq, radius, angle_threshold, dout);
+    finish_host(ctx, nq, {{out, dout, 1}}, pfx::kRepBoundary, pfx::kRepBoundary);  // (Rows carries any row type)
+  }
+  PFX_API_END(ctx)
+}
+
 // Both shape contexts' rule.  `normals_set`: the 3DSC needs the surface normals, the USC has none;
 // `frames_set`: the USC needs the frames, the 3DSC has none.
 static void sc_rule(const char* what, In3 s, bool normals_set, int64_t n_surface, In3 q, bool frames_set, int64_t nq,

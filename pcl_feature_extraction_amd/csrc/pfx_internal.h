@@ -132,7 +132,7 @@ struct GridView {
 // call, resolved in this order.
 enum ReportSlot {
   kRepFpfh, kRepPfh, kRepSpin, kRepIgrad, kRepRift, kRepIspin, kRepSc, kRepLrf, kRepMoments, kRepPcurv, kRepBoard,
-  kReportSlots
+  kRepBoundary, kReportSlots
 };
 constexpr int kReportWords = 16;  // ints of a slot, on the device and in pinned memory
 struct Reports {
@@ -369,7 +369,7 @@ void report_post(pfx_ctx* ctx, ReportSlot slot, const int* words, int n = kRepor
 // After a synchronisation of ctx->stream: the pending slots of [first, last] in order, each through
 // its family's finish step (*_report: the words to ctx->stats, and the Error it throws for them).  A
 // throw clears the slot's sticky device words (reported once) and leaves the later slots pending.
-void reports_resolve(pfx_ctx* ctx, ReportSlot first = kRepFpfh, ReportSlot last = kRepBoard);
+void reports_resolve(pfx_ctx* ctx, ReportSlot first = kRepFpfh, ReportSlot last = kRepBoundary);
 void fpfh_report(pfx_ctx* ctx, const int* h);
 void pfh_report(pfx_ctx* ctx, const int* h);
 void spin_report(pfx_ctx* ctx, const int* h);
@@ -381,6 +381,7 @@ void lrf_report(pfx_ctx* ctx, const int* h);
 void moments_report(pfx_ctx* ctx, const int* h);
 void pcurv_report(pfx_ctx* ctx, const int* h);
 void board_report(pfx_ctx* ctx, const int* h);
+void boundary_report(pfx_ctx* ctx, const int* h);
 void fpfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
               const float* sny, const float* snz, int64_t ns, const float* qx, const float* qy,
               const float* qz, int64_t nq, int same, double r, float* out,
@@ -457,6 +458,11 @@ void board_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, 
                const float* snz, int64_t ns, const float* qx, const float* qy, const float* qz, int64_t nq, double r,
                const pfx_board_params& prm, float* rf);
 int board_cap_small();
+// boundary points (pfx_boundary.hip): the normals are the queries'; out: nq bytes, 0, 1 or
+// PFX_BOUNDARY_NO_NEIGHBORS.  No capacity: the neighbours are not sorted, so none are kept.
+void boundary_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, const float* qx,
+                  const float* qy, const float* qz, const float* qnx, const float* qny, const float* qnz, int64_t nq,
+                  double r, float angle_threshold, uint8_t* out);
 // boost::mt19937 through uniform_01<float>: n floats of the stream of `seed` after `skip` floats
 void rng_uniform01(uint32_t seed, int64_t skip, int64_t n, float* out);
 void range_image_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,

@@ -15,7 +15,7 @@ const SlotInfo kSlots[kReportSlots] = {
     {"fpfh_err", 1, fpfh_report},       {"pfh_err", 1, pfh_report},     {"spin_err", 4, spin_report},
     {"igrad_err", 4, igrad_report},     {"rift_err", 4, rift_report},   {"ispin_err", 4, ispin_report},
     {"sc_err", 4, sc_report},           {"sc_lrf_err", 4, lrf_report},  {"moments_err", 4, moments_report},
-    {"pcurv_err", 4, pcurv_report},     {"board_err", 4, board_report},
+    {"pcurv_err", 4, pcurv_report},     {"board_err", 4, board_report}, {"boundary_err", 0, boundary_report},
 };
 
 }  // namespace
