@@ -343,7 +343,10 @@ pfx_status pfx_fpfh_support_ball_dev(pfx_ctx* ctx, const float* d_sx, const floa
 /* ---- SHOT-352: SHOTEstimationOMP + SHOTLocalReferenceFrameEstimation ---------------- */
 /* desc: nq x 352, rf: nq x 9 (x_axis, y_axis, z_axis) -- SHOT352::{descriptor, rf}.
  * A null surface or normal array with n_surface > 0, or a null query array with nq > 0, is
- * PFX_ERR_INVALID ("shot: invalid arguments") before any copy or launch, in both forms. */
+ * PFX_ERR_INVALID ("shot: invalid arguments") before any copy or launch, in both forms.
+ * Statistics of the last call: "shot_neighbors" (sum of the neighbourhood sizes), "shot_queued"
+ * (queries with more than 2048 neighbours, which the split kernels pass on to the one-workgroup
+ * kernel). */
 pfx_status pfx_shot(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz,
                     const float* snx, const float* sny, const float* snz, int64_t n_surface,
                     const float* qx, const float* qy, const float* qz, int64_t nq,

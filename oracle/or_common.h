@@ -8,9 +8,11 @@
 //
 //      *** parity vs real PCL is UNPINNED ***
 //
-//  The restatement is pinned only by analytic known-answer tests (tests/test_oracle.py) and the regression
-//  fixtures tests/golden/oracle_small.npz
-//  and is the checker the HIP product is compared against.
+//  The restatement is pinned by analytic known-answer tests (tests/test_oracle.py), by the
+//  regression fixtures tests/golden/oracle_small.npz and, for normals, FPFH-33 and SHOT-352, by
+//  float64 statements of the definitions written independently of it (tests/f64_ref.py, held
+//  to measured bounds in tests/test_f64_ref.py; DESIGN.md "Float64 statements of normals, FPFH
+//  and SHOT"), and is the checker the HIP product is compared against.
 //
 //  Floating-point contract (every oracle TU is built with -O2 -ffp-contract=off, x86-64
 //  SSE2, no -march): IEEE binary32/64, left-to-right evaluation, no FMA.  Eigen 3.2

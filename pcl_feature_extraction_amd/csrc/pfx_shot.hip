@@ -264,12 +264,15 @@ void shot_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, c
         g, snx, sny, snz, qx, qy, qz, nq, over, n_over, nullptr, nullptr, r, desc, rf, err, nbr);
     check_launch("k_shot");
   }
-  int h = 0;
+  int h2[2] = {0, 0};  // err (a list beyond kCap), n_over (the lists the split kernels passed on)
   unsigned long long h_nbr = 0;
-  PFX_HIP(hipMemcpyAsync(&h, err, sizeof(int), hipMemcpyDeviceToHost, st));
+  PFX_HIP(hipMemcpyAsync(h2, err, sizeof(h2), hipMemcpyDeviceToHost, st));
   PFX_HIP(hipMemcpyAsync(&h_nbr, nbr, sizeof(h_nbr), hipMemcpyDeviceToHost, st));
   PFX_HIP(hipStreamSynchronize(st));
+  const int h = h2[0];
   ctx->stats["shot_neighbors"] = (int64_t)h_nbr;
+  // the queries the split kernels passed on to the fused kernel (lists above kCapSmall)
+  ctx->stats["shot_queued"] = (int64_t)h2[1];
 #ifdef PFX_SHOT_PROFILE
   {
     unsigned long long pr[16];

@@ -2,8 +2,10 @@
 
 The reference holds no golden vectors for this path: the oracle is pinned by
 (1) analytic answers (planes, spheres, strict radius boundary, FLANN order, normalisation of the
-descriptors), (2) the invariances PCL's descriptors have by construction, and (3) the committed
-regression fixtures under tests/golden/ (tests/golden/make_golden.py).  Parity of the oracle
+descriptors), (2) the invariances PCL's descriptors have by construction, (3) the committed
+regression fixtures under tests/golden/ (tests/golden/make_golden.py), and (4), for normals,
+FPFH-33 and SHOT-352, float64 statements of their definitions written independently of the
+restatement (tests/f64_ref.py, compared in tests/test_f64_ref.py).  Parity of the oracle
 against real PCL itself stays unpinned (PCL is absent from every machine in this pipeline).
 """
 import os
