@@ -50,6 +50,8 @@
  *                          (keypoints.h:212-216, tools.h:61-77)
  *   pfx_narf_keypoints* <- RangeImageBorderExtractor + NarfKeypoint::compute
  *                          (keypoints.h:219-224)
+ *   pfx_narf_descriptors* <- NarfDescriptor::compute (evaluation.cpp:613-648)
+ *   pfx_point_indices*  <- Tools::getIndices (tools.h:91-102)
  *   pfx_radius_search*  <- search::KdTree<PointXYZRGB>::radiusSearch (features.h:192,
  *                          tools.h:29; FLANN order: (d^2, index) ascending, strict d^2 < r^2)
  *   pfx_nearest_descriptors_dev <- Features<T>::getCorrespondences (features.h:255-273):
@@ -764,6 +766,67 @@ pfx_status pfx_narf_keypoints_dev(pfx_ctx* ctx, const float* d_x, const float* d
  * width*height of that call's camera: any other count is PFX_ERR_CAPACITY and nothing is written.
  * A NARF call that fails leaves no images behind (PFX_ERR_INVALID until the next one succeeds). */
 pfx_status pfx_narf_debug_image(pfx_ctx* ctx, const char* which, void* out, int64_t count);
+
+/* ---- NARF descriptors: NarfDescriptor (evaluation.cpp:613-648) ---------------------------- */
+/* The 36-float NARF descriptor (PCL's defaults: descriptor length 36, a 10 x 10 patch; nothing
+ * else is offered) of the entries of pixel_idx (y * width + x) on the planar range image of the
+ * cloud and camera, which the call builds itself.  DESIGN.md "NARF descriptors: the contract"
+ * states every operation; the CPU restatement of that text is the truth the kernel is tested
+ * against bit for bit (parity with PCL itself is unpinned).  All in float32 left to right without
+ * FMA contraction.  For every entry, in order:
+ *   validity   a negative index, one beyond the image, or a pixel without a finite range: no row
+ *              ("narf_desc_invalid_pixels").
+ *   pose       getNormalBasedUprightTransformation (point, support_size / 2): the weighted
+ *              VectorAverage3f of the ring pixels within support_size / 2, its smallest
+ *              eigenvector the normal; with 10 samples or fewer getNormalForClosestNeighbors
+ *              ("narf_desc_fallback_normals"); no normal, or a frame that is not finite (a normal
+ *              along (0, 1, 0)): no row ("narf_desc_pose_failed").
+ *   patch      getInterpolatedSurfaceProjection (pose, 10, support_size), unseen cells in front of
+ *              something further than support_size / 2 behind set to +inf
+ *              ("narf_desc_background_cells"), blurred by getBlurredSurfacePatch (20, 1).
+ *   rows       rotation_invariant == 0: one row, extractDescriptor (36) at rotation 0 with the pose
+ *              above.  Otherwise one row for each of getRotations' 0 to 5 rotations rho, in the
+ *              order they are chosen: the descriptor at rho and Rz (-rho) * pose.  A perfectly
+ *              flat patch has no rotation and so no row.
+ * desc: cap x 36; pose: cap x 12, the row-major 3 x 4 [R | t] that takes world to patch
+ * coordinates; row_key: cap, the entry of pixel_idx a row came from.  Rows come in entry order; cap
+ * = 5 nk never overflows.  *n_out = the number of rows; more than cap: PFX_ERR_CAPACITY, nothing
+ * written but *n_out, the size needed.  A null required pointer, a negative size, support_size <= 0
+ * or NaN, nk above 2^28: PFX_ERR_INVALID before anything is copied or launched; so is a camera beyond
+ * pfx_narf_keypoints' bounds, and noise_level != 0 is PFX_ERR_UNSUPPORTED.  nk == 0 gives no row; n
+ * == 0 an empty image, every entry invalid.  Statistics: "narf_desc_rows" and the four above,
+ * "narf_desc_ring_max" (the largest ring radius walked by the pose and the patch). */
+typedef struct pfx_narf_desc_params {
+  float support_size;         /* -1: must be set > 0 (the reference passes its support_size) */
+  int32_t rotation_invariant; /* 1 */
+} pfx_narf_desc_params;
+void pfx_narf_desc_params_default(pfx_narf_desc_params* p);
+pfx_status pfx_narf_descriptors(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
+                                const pfx_camera* cam, const int32_t* pixel_idx, int64_t nk,
+                                const pfx_narf_desc_params* params, float* desc, float* pose, int32_t* row_key,
+                                int64_t cap, int64_t* n_out);
+/* Device pointers (pixel_idx, the outputs and the count d_n_out included), stream-ordered on the ctx
+ * stream, no host synchronisation.  With more rows than cap the first cap rows are written and
+ * *d_n_out is the full count; the statistics come with the next synchronisation of the ctx. */
+pfx_status pfx_narf_descriptors_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z, int64_t n,
+                                    const pfx_camera* cam, const int32_t* d_pixel_idx, int64_t nk,
+                                    const pfx_narf_desc_params* params, float* d_desc, float* d_pose,
+                                    int32_t* d_row_key, int64_t cap, int64_t* d_n_out);
+
+/* ---- Tools::getIndices (tools.h:91-102) --------------------------------------------------- */
+/* For each keypoint i in order, every cloud index j ascending with |kx[i] - x[j]| < tol and the
+ * same in y and z (Tools::areEqual; the reference's tol is 1e-4f).  A NaN matches nothing; a
+ * keypoint may give none or several indices.  *n_out = their number; more than cap:
+ * PFX_ERR_CAPACITY, nothing written but *n_out.  A null required pointer, a negative size, tol NaN
+ * or n >= 2^31: PFX_ERR_INVALID before anything is copied or launched. */
+pfx_status pfx_point_indices(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
+                             const float* kx, const float* ky, const float* kz, int64_t nk, float tol, int32_t* out,
+                             int64_t cap, int64_t* n_out);
+/* Device pointers, stream-ordered, no host synchronisation: the first cap indices and, in
+ * *d_n_out (device), the full count. */
+pfx_status pfx_point_indices_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z, int64_t n,
+                                 const float* d_kx, const float* d_ky, const float* d_kz, int64_t nk, float tol,
+                                 int32_t* d_out, int64_t cap, int64_t* d_n_out);
 
 /* Test hook of the uniform grid (host buffers): builds the normal-radius grid of a cloud and
  * copies it out.

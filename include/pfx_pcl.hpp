@@ -228,6 +228,9 @@ struct ReferenceFrame { float x_axis[3], y_axis[3], z_axis[3]; };
 // pcl::Boundary: one byte
 struct Boundary { uint8_t boundary_point = 0; };
 static_assert(sizeof(Boundary) == 1, "pcl::Boundary is one byte");
+// (PCL's Narf36: the patch's position and orientation in the world, then the descriptor)
+struct Narf36 { float x = 0, y = 0, z = 0, roll = 0, pitch = 0, yaw = 0; float descriptor[36] = {}; };
+static_assert(sizeof(Narf36) == 42 * sizeof(float), "pcl::Narf36 is 42 floats");
 
 // pcl::PCLException, as far as the facade throws it (SpinImageEstimation where PCL's throws)
 class PCLException : public std::runtime_error {
@@ -1209,6 +1212,78 @@ class NarfKeypoint {
   Parameters parameters_;
 };
 
+// ---- NARF descriptors (evaluation.cpp:613-648) ------------------------------------------------
+// NarfDescriptor (range image, indices): compute() -> one Narf36 per rotation of every index
+// (pfx_narf_descriptors on the cloud and camera the RangeImagePlanar keeps; the indices are PIXEL
+// indices y * width + x, whatever the caller took them from).  With rotation_invariant an index
+// gives 0 to 5 rows, so the rows are not one per index: getRowIndices() says which entry of the
+// index vector each row came from.  A row's x, y, z and roll, pitch, yaw are those of the inverse of
+// its pose (Narf::copyToNarf36: the patch's frame in the world).  A missing range image or index
+// vector, support_size <= 0: PCL_ERROR and an empty output.
+class NarfDescriptor {
+ public:
+  struct Parameters {
+    float support_size = -1.0f;
+    bool rotation_invariant = true;
+  };
+  explicit NarfDescriptor(const RangeImage* range_image = nullptr, const std::vector<int>* indices = nullptr) {
+    setRangeImage(range_image, indices);
+  }
+  void setRangeImage(const RangeImage* range_image, const std::vector<int>* indices = nullptr) {
+    range_image_ = dynamic_cast<const RangeImagePlanar*>(range_image);
+    indices_ = indices;
+  }
+  Parameters& getParameters() { return parameters_; }
+  const std::vector<int>& getRowIndices() const { return row_keys_; }
+  void compute(PointCloud<Narf36>& out) {
+    out.clear();
+    row_keys_.clear();
+    if (!range_image_ || !indices_ || !(parameters_.support_size > 0.0f)) {
+      PCL_ERROR("[pcl::NarfDescriptor::compute] needs a RangeImagePlanar, an index vector and support_size > 0\n");
+      return;
+    }
+    if (!detail::context()) return;
+    pfx_narf_desc_params p;
+    pfx_narf_desc_params_default(&p);
+    p.support_size = parameters_.support_size;
+    p.rotation_invariant = parameters_.rotation_invariant ? 1 : 0;
+    const detail::SoA& c = range_image_->source_cloud();
+    const pfx_camera cam = range_image_->camera();
+    const std::vector<int32_t> pix(indices_->begin(), indices_->end());
+    const int64_t cap = 5 * (int64_t)pix.size();
+    std::vector<float> desc((size_t)cap * 36), pose((size_t)cap * 12);
+    std::vector<int32_t> key((size_t)cap);
+    int64_t m = 0;
+    if (!detail::ok(pfx_narf_descriptors(detail::context(), c.x.data(), c.y.data(), c.z.data(), (int64_t)c.x.size(), &cam,
+                                         pix.data(), (int64_t)pix.size(), &p, desc.data(), pose.data(), key.data(), cap,
+                                         &m),
+                    "NarfDescriptor"))
+      return;
+    out.points.resize((size_t)m);
+    for (int64_t r = 0; r < m; ++r) {
+      const float* a = &pose[(size_t)r * 12];  // [R | t]; its inverse: R^T, -(R^T t)
+      Narf36& o = out.points[(size_t)r];
+      o.x = -((a[0] * a[3] + a[4] * a[7]) + a[8] * a[11]);
+      o.y = -((a[1] * a[3] + a[5] * a[7]) + a[9] * a[11]);
+      o.z = -((a[2] * a[3] + a[6] * a[7]) + a[10] * a[11]);
+      // getEulerAngles of the inverse's rotation m = R^T: atan2 (m21, m22), asin (-m20), atan2 (m10, m00)
+      o.roll = std::atan2(a[6], a[10]);
+      o.pitch = std::asin(-a[2]);
+      o.yaw = std::atan2(a[1], a[0]);
+      for (int k = 0; k < 36; ++k) o.descriptor[k] = desc[(size_t)r * 36 + k];
+    }
+    row_keys_.assign(key.begin(), key.begin() + m);
+    out.width = (uint32_t)m;
+    out.height = 1;
+  }
+
+ private:
+  const RangeImagePlanar* range_image_ = nullptr;
+  const std::vector<int>* indices_ = nullptr;
+  Parameters parameters_;
+  std::vector<int> row_keys_;
+};
+
 // ---- ISS keypoints (keypoints.h:177-189) ------------------------------------------------------
 // ISSKeypoint3D<In, Out, NormalT>: the reference's setters, compute() -> the keypoints' xyz in
 // index order (pfx_iss_keypoints; PCL pushes them from an OpenMP loop).  A
@@ -1418,6 +1493,11 @@ template <> struct DescriptorLayout<MomentInvariants> { static constexpr int dim
 template <> struct DescriptorLayout<PrincipalCurvatures> { static constexpr int dim = 3, stride = 5; };
 // (the same rule for the nine floats of a ReferenceFrame: the x axis alone is compared)
 template <> struct DescriptorLayout<ReferenceFrame> { static constexpr int dim = 3, stride = 9; };
+// (Narf36's representation: the 36 descriptor floats behind x, y, z, roll, pitch, yaw)
+template <> struct DescriptorLayout<Narf36> { static constexpr int dim = 36, stride = 42, offset = 6; };
+// the float of a point the descriptor starts at: a layout's `offset`, 0 for a layout without one
+template <typename L, typename = void> struct LayoutOffset { static constexpr int value = 0; };
+template <typename L> struct LayoutOffset<L, decltype((void)L::offset)> { static constexpr int value = L::offset; };
 }  // namespace detail
 
 // KdTreeFLANN<FeatureT> with nearestKSearch(k = 1), as the reference uses it (features.h:258-272):
@@ -1448,10 +1528,12 @@ class KdTreeFLANN {
       dist_.assign(cloud.size(), detail::nanf());
       std::lock_guard<std::mutex> lock(detail::context_mutex());
       typedef detail::DescriptorLayout<PointT> L;
+      constexpr int offset = detail::LayoutOffset<L>::value;
       if (!detail::context() ||
-          !detail::ok(pfx_nearest_descriptors(detail::context(), reinterpret_cast<const float*>(cloud.points.data()),
+          !detail::ok(pfx_nearest_descriptors(detail::context(),
+                                              reinterpret_cast<const float*>(cloud.points.data()) + offset,
                                               (int64_t)cloud.size(), L::stride,
-                                              reinterpret_cast<const float*>(target_->points.data()),
+                                              reinterpret_cast<const float*>(target_->points.data()) + offset,
                                               (int64_t)target_->size(), L::stride, L::dim, idx_.data(), dist_.data()),
                       "KdTreeFLANN"))
         idx_.assign(cloud.size(), -1);

@@ -100,6 +100,14 @@ class BoardParams(ctypes.Structure):
     ]
 
 
+class NarfDescParams(ctypes.Structure):
+    """pfx_narf_desc_params (NarfDescriptor::Parameters)."""
+    _fields_ = [
+        ("support_size", ctypes.c_float),
+        ("rotation_invariant", ctypes.c_int32),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "pfx_narf_params_default": (None, [ctypes.POINTER(NarfParams)]),
@@ -202,6 +210,15 @@ _SIGS = {
     "pfx_narf_keypoints_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(Camera),
                                        ctypes.POINTER(NarfParams), c_vp, c_i64, c_i64p]),
     "pfx_narf_debug_image": (c_int, [c_vp, ctypes.c_char_p, c_vp, c_i64]),
+    "pfx_narf_desc_params_default": (None, [ctypes.POINTER(NarfDescParams)]),
+    "pfx_narf_descriptors": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(Camera), c_vp, c_i64,
+                                     ctypes.POINTER(NarfDescParams), c_vp, c_vp, c_vp, c_i64, c_i64p]),
+    "pfx_narf_descriptors_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(Camera), c_vp, c_i64,
+                                         ctypes.POINTER(NarfDescParams), c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "pfx_point_indices": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, ctypes.c_float, c_vp,
+                                  c_i64, c_i64p]),
+    "pfx_point_indices_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, ctypes.c_float, c_vp,
+                                      c_i64, c_vp]),
     "pfx_grid_debug": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_dbl, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_i64,
                                c_vp, c_vp]),
     "pfx_gather_points_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp,
@@ -250,8 +267,8 @@ _SIGS = {
 
 # entry points an older library loaded through PFX_LIB (A/B runs against a previous build) may lack:
 # test hooks, ICP, spin images, intensity gradients, RIFT, intensity spin images, the shape contexts,
-# moment invariants, principal curvatures, BOARD frames and boundary points (calling a missing one raises
-# AttributeError there)
+# moment invariants, principal curvatures, BOARD frames, boundary points, NARF descriptors and the point
+# indices (calling a missing one raises AttributeError there)
 _OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_icp_dev",
                    "pfx_spin_params_default", "pfx_spin_image", "pfx_spin_image_dev",
                    "pfx_intensity_gradient", "pfx_intensity_gradient_dev", "pfx_rift", "pfx_rift_dev",
@@ -260,7 +277,8 @@ _OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_i
                    "pfx_shot_lrf_dev", "pfx_rng_uniform01", "pfx_moment_invariants", "pfx_moment_invariants_dev",
                    "pfx_principal_curvatures", "pfx_principal_curvatures_dev",
                    "pfx_board_params_default", "pfx_board_lrf", "pfx_board_lrf_dev",
-                   "pfx_boundary", "pfx_boundary_dev"}
+                   "pfx_boundary", "pfx_boundary_dev", "pfx_narf_desc_params_default", "pfx_narf_descriptors",
+                   "pfx_narf_descriptors_dev", "pfx_point_indices", "pfx_point_indices_dev"}
 
 _lib = None
 

@@ -44,6 +44,15 @@ def narf_params(support_size=0.2, **kw) -> N.NarfParams:
     return p
 
 
+def narf_desc_params(support_size=0.2, rotation_invariant=True) -> N.NarfDescParams:
+    """pfx_narf_desc_params; rotation_invariant is PCL's default (pfx_narf_desc_params_default), the
+    support size the reference's."""
+    p = N.NarfDescParams()
+    N.lib().pfx_narf_desc_params_default(ctypes.byref(p))
+    p.support_size, p.rotation_invariant = float(support_size), int(bool(rotation_invariant))
+    return p
+
+
 def icp_params(**kw) -> N.IcpParams:
     """pfx_icp_params with PCL's defaults (sqrt(DBL_MAX), 10, 0, -DBL_MAX); the reference's icpAlign
     sets max_correspondence_distance=0.07, max_iterations=100, transformation_epsilon=1e-6,
@@ -94,6 +103,10 @@ def rgb_to_intensity(rgb) -> np.ndarray:
     b = (c & 255).astype(np.float32)
     return (np.float32(0.299) * r + np.float32(0.587) * g) + np.float32(0.114) * b
 
+
+#: result of Context.narf_descriptors: desc (m, 36), pose (m, 12) the row-major 3 x 4 world -> patch
+#: transforms, keypoint (m,) the entry of pixel_idx each row came from
+NarfDescriptors = collections.namedtuple("NarfDescriptors", "desc pose keypoint")
 
 #: result of Context.icp / icp_dev; state: 0 not converged, 1 iterations, 2 transform, 3 absolute
 #: MSE, 4 relative MSE, 5 no correspondences (pfx.h PFX_ICP_*); aligned: (x, y, z) or None
@@ -453,6 +466,39 @@ class Context:
                                                  ctypes.byref(params), _ptr(out), cap, ctypes.byref(nout)))
         return out[: nout.value].copy()
 
+    def narf_descriptors(self, x, y, z, pixel_idx, params=None, cam=None):
+        """NarfDescriptor (pfx_narf_descriptors) at the pixels pixel_idx (y * width + x) of the cloud's
+        planar range image: NarfDescriptors(desc, pose, keypoint).  An entry gives 0 to 5 rows (one or
+        none without rotation invariance), in entry order."""
+        cam = cam or camera()
+        params = params or narf_desc_params()
+        x, y, z = map(_f32, (x, y, z))
+        pix = np.ascontiguousarray(pixel_idx, dtype=np.int32)
+        cap = 5 * len(pix)
+        desc, pose = np.empty((cap, 36), np.float32), np.empty((cap, 12), np.float32)
+        key = np.empty(cap, np.int32)
+        nout = ctypes.c_int64()
+        self._check(self._lib.pfx_narf_descriptors(self.h, _ptr(x), _ptr(y), _ptr(z), len(x), ctypes.byref(cam),
+                                                   _ptr(pix), len(pix), ctypes.byref(params), _ptr(desc), _ptr(pose),
+                                                   _ptr(key), cap, ctypes.byref(nout)))
+        m = nout.value
+        return NarfDescriptors(desc[:m].copy(), pose[:m].copy(), key[:m].copy())
+
+    def point_indices(self, x, y, z, kx, ky, kz, tol=1e-4):
+        """Tools::getIndices (pfx_point_indices): for each keypoint in order, every cloud index ascending
+        within tol of it on all three axes; (m,) int32."""
+        x, y, z, kx, ky, kz = map(_f32, (x, y, z, kx, ky, kz))
+        cap = max(64, 2 * len(kx))
+        while True:
+            out = np.empty(cap, np.int32)
+            nout = ctypes.c_int64()
+            code = self._lib.pfx_point_indices(self.h, _ptr(x), _ptr(y), _ptr(z), len(x), _ptr(kx), _ptr(ky), _ptr(kz),
+                                               len(kx), float(tol), _ptr(out), cap, ctypes.byref(nout))
+            if code != N.PFX_ERR_CAPACITY:
+                self._check(code)
+                return out[: nout.value].copy()
+            cap = nout.value  # the size the call asked for
+
     def narf_debug_image(self, which, width=640, height=480):
         dt = np.uint32 if which == "border_traits" else np.float32
         out = np.empty(width * height, dtype=dt)
@@ -697,6 +743,31 @@ class Context:
                                                      ctypes.byref(cam), ctypes.byref(params), _ptr(out), cap,
                                                      ctypes.byref(nout)))
         return out[: nout.value].copy()
+
+    def narf_descriptors_dev(self, x, y, z, pixel_idx, desc, pose, row_key, params=None, cam=None):
+        """pfx_narf_descriptors_dev: pixel_idx an int32 device tensor, desc (cap, 36) / pose (cap, 12)
+        float32 and row_key (cap,) int32 device tensors.  Returns the (1,) int64 device tensor of the
+        row count (the full count, also when it exceeds cap and only cap rows were written); no host
+        synchronisation, the statistics come with the next synchronize()."""
+        import torch
+        cam = cam or camera()
+        params = params or narf_desc_params()
+        cap = min(desc.shape[0], pose.shape[0], row_key.shape[0])
+        count = torch.empty(1, dtype=torch.int64, device=x.device)  # (always written by the call, on its stream)
+        self._check(self._lib.pfx_narf_descriptors_dev(self.h, _ptr(x), _ptr(y), _ptr(z), x.numel(), ctypes.byref(cam),
+                                                       _ptr(pixel_idx), pixel_idx.numel(), ctypes.byref(params),
+                                                       _ptr(desc), _ptr(pose), _ptr(row_key), cap, _ptr(count)))
+        return count
+
+    def point_indices_dev(self, x, y, z, kx, ky, kz, out, tol=1e-4):
+        """pfx_point_indices_dev: out an int32 device tensor; returns the (1,) int64 device tensor of the
+        full count (out holds the first out.numel() indices).  No host synchronisation."""
+        import torch
+        count = torch.empty(1, dtype=torch.int64, device=x.device)  # (always written by the call, on its stream)
+        self._check(self._lib.pfx_point_indices_dev(self.h, _ptr(x), _ptr(y), _ptr(z), x.numel(), _ptr(kx), _ptr(ky),
+                                                    _ptr(kz), kx.numel(), float(tol), _ptr(out), out.numel(),
+                                                    _ptr(count)))
+        return count
 
     def gather_points_dev(self, x, y, z, idx_np, kx, ky, kz):
         idx = np.ascontiguousarray(idx_np, dtype=np.int32)

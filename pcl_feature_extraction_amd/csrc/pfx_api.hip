@@ -1,5 +1,6 @@
 // pfx_api.hip -- the extern "C" boundary (include/pfx.h).  Host-pointer entry points stage
 // through ctx-owned device buffers and call the stream-ordered *_dev implementations.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -151,6 +152,12 @@ void pfx_narf_params_default(pfx_narf_params* p) {
   p->pixel_radius_border_direction = 2;
   p->minimum_border_probability = 0.8f;
   p->pixel_radius_principal_curvature = 2;
+}
+
+void pfx_narf_desc_params_default(pfx_narf_desc_params* p) {
+  if (!p) return;
+  p->support_size = -1.0f;
+  p->rotation_invariant = 1;
 }
 
 void pfx_camera_default(pfx_camera* c) {
@@ -1173,6 +1180,91 @@ pfx_status pfx_narf_debug_image(pfx_ctx* ctx, const char* which, void* out, int6
   check_ctx(ctx);
   if (!which || !out) throw Error(PFX_ERR_INVALID, "narf_debug: null argument");
   pfx::narf_debug(ctx, which, out, count);
+  PFX_API_END(ctx)
+}
+
+// The cloud is the surface side and pixel_idx the query side of the one argument rule; the outputs
+// are needed where cap allows a row.  Then the family's own rules: the camera's.
+static void narf_desc_rule(In3 c, int64_t n, const pfx_camera* cam, const int32_t* pixel_idx, int64_t nk,
+                           const pfx_narf_desc_params* p, const float* desc, const float* pose, const int32_t* row_key,
+                           int64_t cap, const int64_t* n_out) {
+  args_rule("narf_descriptors", n, all_set(c), nk, all_set(pixel_idx),
+            cam && p && n_out && cap >= 0 && (cap == 0 || all_set(desc, pose, row_key)) && nk <= (int64_t(1) << 28) &&
+                p->support_size > 0.0f);  // (a NaN support_size fails the comparison)
+  pfx::narf_camera_rule(*cam, "narf_descriptors");
+}
+
+pfx_status pfx_narf_descriptors_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z, int64_t n,
+                                    const pfx_camera* cam, const int32_t* d_pixel_idx, int64_t nk,
+                                    const pfx_narf_desc_params* params, float* d_desc, float* d_pose,
+                                    int32_t* d_row_key, int64_t cap, int64_t* d_n_out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  narf_desc_rule({d_x, d_y, d_z}, n, cam, d_pixel_idx, nk, params, d_desc, d_pose, d_row_key, cap, d_n_out);
+  pfx::narf_desc_dev(ctx, d_x, d_y, d_z, n, *cam, d_pixel_idx, nk, *params, d_desc, d_pose, d_row_key, cap, d_n_out);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_narf_descriptors(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
+                                const pfx_camera* cam, const int32_t* pixel_idx, int64_t nk,
+                                const pfx_narf_desc_params* params, float* desc, float* pose, int32_t* row_key,
+                                int64_t cap, int64_t* n_out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  narf_desc_rule({x, y, z}, n, cam, pixel_idx, nk, params, desc, pose, row_key, cap, n_out);
+  *n_out = 0;
+  if (nk) {  // (without entries nothing is staged, run or resolved)
+    const Dev3 c = stage3(ctx, "in_", x, y, z, n);
+    int32_t* dpix = ctx->buf("in_pixel_idx").as<int32_t>(nk);
+    PFX_HIP(hipMemcpyAsync(dpix, pixel_idx, sizeof(int32_t) * nk, hipMemcpyHostToDevice, ctx->stream));
+    const int64_t rows = std::min<int64_t>(cap, 5 * nk);  // (no entry gives more than 5)
+    float* ddesc = ctx->buf("out_narf_desc").as<float>(rows * 48 + 1);
+    float* dpose = ddesc + rows * 36;
+    int32_t* dkey = ctx->buf("out_narf_desc_key").as<int32_t>(rows + 1);
+    int64_t* dn = ctx->buf("out_count").as<int64_t>(1);
+    pfx::narf_desc_dev(ctx, c.x, c.y, c.z, n, *cam, dpix, nk, *params, ddesc, dpose, dkey, rows, dn);
+    PFX_HIP(hipMemcpyAsync(n_out, dn, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    finish_host(ctx, 0, {}, pfx::kRepNarfDesc, pfx::kRepNarfDesc);
+    if (*n_out > cap) throw Error(PFX_ERR_CAPACITY, "narf_descriptors: output capacity too small");
+    finish_host(ctx, *n_out, {{desc, ddesc, 36}, {pose, dpose, 12}, {row_key, dkey, 1}});
+  }
+  PFX_API_END(ctx)
+}
+
+static void point_indices_rule(In3 c, int64_t n, In3 k, int64_t nk, float tol, const int32_t* out, int64_t cap,
+                               const int64_t* n_out) {
+  args_rule("point_indices", n, all_set(c), nk, all_set(k),
+            n_out && cap >= 0 && (cap == 0 || out) && !std::isnan(tol) && n < (int64_t(1) << 31));
+}
+
+pfx_status pfx_point_indices_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z, int64_t n,
+                                 const float* d_kx, const float* d_ky, const float* d_kz, int64_t nk, float tol,
+                                 int32_t* d_out, int64_t cap, int64_t* d_n_out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  point_indices_rule({d_x, d_y, d_z}, n, {d_kx, d_ky, d_kz}, nk, tol, d_out, cap, d_n_out);
+  pfx::point_indices_dev(ctx, d_x, d_y, d_z, n, d_kx, d_ky, d_kz, nk, tol, d_out, cap, d_n_out);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_point_indices(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, const float* kx,
+                             const float* ky, const float* kz, int64_t nk, float tol, int32_t* out, int64_t cap,
+                             int64_t* n_out) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  point_indices_rule({x, y, z}, n, {kx, ky, kz}, nk, tol, out, cap, n_out);
+  *n_out = 0;
+  if (nk && n) {
+    const Dev3 c = stage3(ctx, "in_", x, y, z, n), k = stage3(ctx, "in_q", kx, ky, kz, nk);
+    const int64_t room = n > INT64_MAX / nk ? cap : std::min<int64_t>(cap, nk * n);  // (every pair at most)
+    int32_t* dout = ctx->buf("out_point_indices").as<int32_t>(room + 1);
+    int64_t* dn = ctx->buf("out_count").as<int64_t>(1);
+    pfx::point_indices_dev(ctx, c.x, c.y, c.z, n, k.x, k.y, k.z, nk, tol, dout, room, dn);
+    PFX_HIP(hipMemcpyAsync(n_out, dn, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    finish_host(ctx, 0, {});
+    if (*n_out > cap) throw Error(PFX_ERR_CAPACITY, "point_indices: output capacity too small");
+    finish_host(ctx, *n_out, {{out, dout, 1}});
+  }
   PFX_API_END(ctx)
 }
 

@@ -132,7 +132,7 @@ struct GridView {
 // call, resolved in this order.
 enum ReportSlot {
   kRepFpfh, kRepPfh, kRepSpin, kRepIgrad, kRepRift, kRepIspin, kRepSc, kRepLrf, kRepMoments, kRepPcurv, kRepBoard,
-  kRepBoundary, kReportSlots
+  kRepBoundary, kRepNarfDesc, kReportSlots
 };
 constexpr int kReportWords = 16;  // ints of a slot, on the device and in pinned memory
 struct Reports {
@@ -369,7 +369,7 @@ void report_post(pfx_ctx* ctx, ReportSlot slot, const int* words, int n = kRepor
 // After a synchronisation of ctx->stream: the pending slots of [first, last] in order, each through
 // its family's finish step (*_report: the words to ctx->stats, and the Error it throws for them).  A
 // throw clears the slot's sticky device words (reported once) and leaves the later slots pending.
-void reports_resolve(pfx_ctx* ctx, ReportSlot first = kRepFpfh, ReportSlot last = kRepBoundary);
+void reports_resolve(pfx_ctx* ctx, ReportSlot first = kRepFpfh, ReportSlot last = kRepNarfDesc);
 void fpfh_report(pfx_ctx* ctx, const int* h);
 void pfh_report(pfx_ctx* ctx, const int* h);
 void spin_report(pfx_ctx* ctx, const int* h);
@@ -382,6 +382,7 @@ void moments_report(pfx_ctx* ctx, const int* h);
 void pcurv_report(pfx_ctx* ctx, const int* h);
 void board_report(pfx_ctx* ctx, const int* h);
 void boundary_report(pfx_ctx* ctx, const int* h);
+void narf_desc_report(pfx_ctx* ctx, const int* h);
 void fpfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
               const float* sny, const float* snz, int64_t ns, const float* qx, const float* qy,
               const float* qz, int64_t nq, int same, double r, float* out,
@@ -471,6 +472,19 @@ int64_t narf_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, i
                  const pfx_camera& cam, const pfx_narf_params& p, std::vector<int32_t>& out);
 void narf_debug(pfx_ctx* ctx, const std::string& which, void* out, int64_t count);
 void narf_release(pfx_ctx* ctx);
+// the image size pfx_narf_keypoints* and pfx_narf_descriptors* accept (PFX_ERR_INVALID beyond: narf_dev's
+// own check), and with it noise_level != 0 (PFX_ERR_UNSUPPORTED, which narf_dev leaves to
+// range_image_dev) for the entry points that check everything before they launch
+void narf_image_size_rule(const pfx_camera& cam, const char* what);
+void narf_camera_rule(const pfx_camera& cam, const char* what);
+// NARF descriptors and Tools::getIndices (pfx_narf_desc.hip): stream-ordered, no host
+// synchronisation; rows beyond cap are dropped and *d_n_out (device) is the full count
+void narf_desc_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, const pfx_camera& cam,
+                   const int32_t* pixel_idx, int64_t nk, const pfx_narf_desc_params& prm, float* desc, float* pose,
+                   int32_t* row_key, int64_t cap, int64_t* d_n_out);
+void point_indices_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, const float* kx,
+                       const float* ky, const float* kz, int64_t nk, float tol, int32_t* out, int64_t cap,
+                       int64_t* d_n_out);
 pfx_status pcd_read_header(const char* path, pfx_pcd_header* out, std::string& err);
 int64_t pcd_load_xyz_dev(pfx_ctx* ctx, const char* path, float* d_x, float* d_y, float* d_z, int64_t cap,
                          pfx_pcd_header* hdr_out);

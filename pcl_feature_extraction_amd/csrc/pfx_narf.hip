@@ -22,6 +22,7 @@
 #include <cstdio>
 
 #include "pfx_internal.h"
+#include "pfx_range_image.h"
 
 namespace pfx {
 
@@ -64,52 +65,6 @@ struct NarfState {
 };
 
 namespace {
-
-struct Aff { float m[12]; };  // row-major 3x4 [R | t]
-
-struct Img {
-  int w, h;
-  float cx, cy, fx, fy, fxr, fyr;
-  Aff to_world, to_ri;
-};
-
-__device__ __forceinline__ f3 aff_apply(const Aff& a, f3 p) {
-  return mk3(a.m[3] + (a.m[0] * p.x + a.m[1] * p.y + a.m[2] * p.z),
-             a.m[7] + (a.m[4] * p.x + a.m[5] * p.y + a.m[6] * p.z),
-             a.m[11] + (a.m[8] * p.x + a.m[9] * p.y + a.m[10] * p.z));
-}
-
-__device__ __forceinline__ bool in_image(const Img& I, int x, int y) { return x >= 0 && x < I.w && y >= 0 && y < I.h; }
-
-__device__ __forceinline__ f3 calc3d(const Img& I, float ix, float iy, float range) {
-  float dx = (ix + 0.0f - I.cx) * I.fxr, dy = (iy + 0.0f - I.cy) * I.fyr;
-  f3 p;
-  p.z = range / (sqrtf(dx * dx + dy * dy + 1));
-  p.x = dx * p.z;
-  p.y = dy * p.z;
-  return aff_apply(I.to_world, p);
-}
-
-__device__ __forceinline__ void image_point(const Img& I, f3 pt, float& ix, float& iy, float& range) {
-  f3 t = aff_apply(I.to_ri, pt);
-  if (t.z <= 0) { ix = iy = range = -1.0f; return; }
-  range = sqrtf(sqn3(t));
-  ix = I.cx + I.fx * t.x / t.z - 0.0f;
-  iy = I.cy + I.fy * t.y / t.z - 0.0f;
-}
-
-__device__ __forceinline__ float sq_dist(float4 a, float4 b) {  // diff = b - a
-  float dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
-  return dx * dx + dy * dy + dz * dz;
-}
-
-__device__ __forceinline__ float4 get_point(const Img& I, const float4* __restrict__ P, int x, int y) {
-  if (!in_image(I, x, y)) return make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), -INFINITY);
-  return P[y * I.w + x];
-}
-__device__ __forceinline__ bool is_valid(const Img& I, const float4* __restrict__ P, int x, int y) {
-  return in_image(I, x, y) && isfinite(P[y * I.w + x].w);
-}
 
 // ---- range image ---------------------------------------------------------------------------
 __global__ void k_ri_init(uint32_t* __restrict__ direct, uint32_t* __restrict__ fill, int n) {
@@ -154,37 +109,6 @@ __global__ void k_ri_finalize(Img I, const uint32_t* __restrict__ direct, const 
   P[i] = o;
 }
 
-// ---- VectorAverage3f -------------------------------------------------------------------------
-struct VecAvg {
-  int n;
-  float acc_w;
-  f3 mean;
-  float c00, c01, c02, c11, c12, c22;
-  __device__ void init() { n = 0; acc_w = 0.f; mean = mk3(0, 0, 0); c00 = c01 = c02 = c11 = c12 = c22 = 0.f; }
-  __device__ void add(f3 s) {
-    ++n;
-    acc_w += 1.0f;
-    float alpha = 1.0f / acc_w;
-    f3 d = sub3(s, mean);
-    mean = add3(mean, mk3(alpha * d.x, alpha * d.y, alpha * d.z));
-    float om = 1.0f - alpha;
-    // `(1.0f-alpha)*(covariance_(i, j) + alpha*diff[i]*diff[j])`: (alpha * d_i) * d_j
-    c00 = om * (c00 + alpha * d.x * d.x);
-    c01 = om * (c01 + alpha * d.x * d.y);
-    c02 = om * (c02 + alpha * d.x * d.z);
-    c11 = om * (c11 + alpha * d.y * d.y);
-    c12 = om * (c12 + alpha * d.y * d.z);
-    c22 = om * (c22 + alpha * d.z * d.z);
-  }
-  __device__ void pca(float ev[3], f3 evec[3]) const {
-    Sym3 m;
-    m.a00 = c00; m.a01 = c01; m.a02 = c02;
-    m.a10 = c01; m.a11 = c11; m.a12 = c12;
-    m.a20 = c02; m.a21 = c12; m.a22 = c22;
-    eigen33_full(m, evec, ev);
-  }
-};
-
 // RangeImage::getSurfaceInformation (no-jumps part), radius/step from the border parameters
 // surf = (normal_no_jumps, max_neighbor_distance_squared), smean = neighborhood_mean_no_jumps
 __global__ void k_surface(Img I, const float4* __restrict__ P, int radius, int step, int no_of_closest,
@@ -195,38 +119,11 @@ __global__ void k_surface(Img I, const float4* __restrict__ P, int radius, int s
   int y = i / I.w, x = i - y * I.w;
   float4 point = P[i];
   if (!isfinite(point.w)) return;
-  float nd[25];
-  float4 np[25];
-  int cnt = 0;
-  for (int y2 = y - radius; y2 <= y + radius; y2 += step)
-    for (int x2 = x - radius; x2 <= x + radius; x2 += step) {
-      if (!is_valid(I, P, x2, y2) || cnt >= 25) continue;
-      float4 q = P[y2 * I.w + x2];
-      float d = sq_dist(point, q);
-      int j = cnt++;
-      while (j > 0 && d < nd[j - 1]) { nd[j] = nd[j - 1]; np[j] = np[j - 1]; --j; }
-      nd[j] = d;
-      np[j] = q;
-    }
-  int k = cnt < no_of_closest ? cnt : no_of_closest;
-  float maxd2 = nd[k - 1];
-  float lim = maxd2 * 4.0f;
-  VecAvg va;
-  va.init();
-  for (int j = 0; j < cnt; ++j) {
-    if (nd[j] > lim) break;
-    va.add(mk3(np[j].x, np[j].y, np[j].z));
-  }
-  if (va.n < 3) return;
-  float ev[3];
-  f3 evec[3];
-  va.pca(ev, evec);
-  f3 normal = evec[0];
-  f3 sensor = mk3(I.to_world.m[3], I.to_world.m[7], I.to_world.m[11]);
-  f3 view = normalized3(sub3(sensor, mk3(point.x, point.y, point.z)));
-  if (dot3(normal, view) < 0.0f) normal = scale3(normal, -1.0f);
+  f3 normal, mean;
+  float maxd2;
+  if (!surface_information(I, P, x, y, radius, step, no_of_closest, point, normal, mean, maxd2)) return;
   surf[i] = make_float4(normal.x, normal.y, normal.z, maxd2);
-  smean[i] = make_float4(va.mean.x, va.mean.y, va.mean.z, 0.0f);
+  smean[i] = make_float4(mean.x, mean.y, mean.z, 0.0f);
   svalid[i] = 1;
 }
 
@@ -553,14 +450,9 @@ __global__ void k_surface_change(Img I, const float4* __restrict__ P, const floa
 // LDS budget (very close to the sensor) go to the full-image variant.  A pixel touched outside
 // its window raises the error flag (the bound is a checked invariant, not an assumption).
 constexpr int kWinWords = 2048;     // 65,536-pixel window (e.g. 256 x 256)
-constexpr int kFullWords = 9600;    // 640 x 480 bits
+constexpr int kFullWords = kNarfMaxPixels / 32;  // 640 x 480 bits
 constexpr int kQueue = 2048;        // ring buffer of pending pixels
 constexpr int kContribCap = 2048;   // k_interest_ff: contributing pixels compacted per batch (4 KB LDS)
-
-__device__ __forceinline__ float norm_angle(float a) {
-  const float pi = 3.14159265358979323846f;
-  return a >= 0 ? fmodf(a + pi, 2.0f * pi) - pi : -(fmodf(pi - a, 2.0f * pi) - pi);
-}
 
 // Row prefix counts of "contributing" pixels (valid, not shadow/veil, scs >= thr): with
 // thr = min_scs a pixel whose region-grow window holds none of them has interest exactly 0 (no
@@ -1232,31 +1124,6 @@ __global__ void k_valid_bits(const float4* __restrict__ P, int npx, uint32_t* __
 struct HostInterestPoint { float x, y, z, strength; };
 bool host_better(const HostInterestPoint& a, const HostInterestPoint& b) { return a.strength > b.strength; }
 
-Img make_img(const pfx_camera& c) {
-  Img I;
-  I.w = c.width; I.h = c.height;
-  I.cx = c.center_x; I.cy = c.center_y; I.fx = c.focal_length_x; I.fy = c.focal_length_y;
-  I.fxr = 1 / c.focal_length_x; I.fyr = 1 / c.focal_length_y;
-  float F[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-  if (c.coordinate_frame == 1) {
-    float L[4][4] = {{0, 0, 1, 0}, {-1, 0, 0, 0}, {0, -1, 0, 0}, {0, 0, 0, 1}};
-    std::memcpy(F, L, sizeof(F));
-  }
-  float W[4][4];
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j)
-      W[i][j] = ((c.sensor_pose[i * 4 + 0] * F[0][j] + c.sensor_pose[i * 4 + 1] * F[1][j]) +
-                 c.sensor_pose[i * 4 + 2] * F[2][j]) + c.sensor_pose[i * 4 + 3] * F[3][j];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 4; ++j) I.to_world.m[i * 4 + j] = W[i][j];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) I.to_ri.m[i * 4 + j] = W[j][i];
-  for (int i = 0; i < 3; ++i)
-    I.to_ri.m[i * 4 + 3] = -(I.to_ri.m[i * 4 + 0] * W[0][3] + I.to_ri.m[i * 4 + 1] * W[1][3] +
-                             I.to_ri.m[i * 4 + 2] * W[2][3]);
-  return I;
-}
-
 // host mirror of image_point (same float operation order)
 void host_image_point(const Img& I, float px, float py, float pz, float& ix, float& iy) {
   const float* a = I.to_ri.m;
@@ -1319,8 +1186,7 @@ int64_t narf_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, i
   // the whole keypoint call on its stream (host round trips included): a stage timer
   TimeScope total(ctx, "narf", true);
   Img I = make_img(cam);
-  PFX_CHECK(I.w > 0 && I.h > 0 && (int64_t)I.w * I.h <= kFullWords * 32 && I.w <= 1024,
-            "narf: image larger than 640x480 pixels is not supported");
+  narf_image_size_rule(cam, "narf");
   const int npx = I.w * I.h;
   S.w = I.w;
   S.h = I.h;

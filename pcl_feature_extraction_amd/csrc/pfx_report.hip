@@ -16,6 +16,7 @@ const SlotInfo kSlots[kReportSlots] = {
     {"igrad_err", 4, igrad_report},     {"rift_err", 4, rift_report},   {"ispin_err", 4, ispin_report},
     {"sc_err", 4, sc_report},           {"sc_lrf_err", 4, lrf_report},  {"moments_err", 4, moments_report},
     {"pcurv_err", 4, pcurv_report},     {"board_err", 4, board_report}, {"boundary_err", 0, boundary_report},
+    {"narf_desc_err", 0, narf_desc_report},
 };
 
 }  // namespace
