@@ -46,6 +46,9 @@
  *                          ::compute (features.h:175-196, evaluation.cpp:372-393)
  *   pfx_boundary*       <- BoundaryEstimation<PointXYZRGB,Normal,Boundary>::compute
  *                          (features.h:175-196, evaluation.cpp:394-415)
+ *   pfx_cvfh*           <- CVFHEstimation<PointXYZRGB,Normal,VFHSignature308>::compute through the
+ *                          Feature base pointer (features.h:175-196, evaluation.cpp:649-675)
+ *   pfx_smooth_clusters* <- extractEuclideanClustersSmooth, CVFH's clustering stage
  *   pfx_range_image_planar* <- RangeImagePlanar::createFromPointCloudWithFixedSize
  *                          (keypoints.h:212-216, tools.h:61-77)
  *   pfx_narf_keypoints* <- RangeImageBorderExtractor + NarfKeypoint::compute
@@ -745,6 +748,78 @@ pfx_status pfx_boundary_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, 
                             int64_t n_surface, const float* d_qx, const float* d_qy, const float* d_qz,
                             const float* d_qnx, const float* d_qny, const float* d_qnz, int64_t nq,
                             double radius, float angle_threshold, uint8_t* d_out);
+
+/* ---- smooth clusters and CVFH: CVFHEstimation<PointXYZRGB, Normal, VFHSignature308>
+ *      (evaluation.cpp:649-675) -------------------------------------------------------------- */
+/* pfx_smooth_clusters is pcl::extractEuclideanClustersSmooth: the connected components of the graph
+ * whose edges i - j (i != j) are the pairs with
+ *   d^2 < (float)(t t), t = (double)tolerance, d^2 = ((0 + dx^2) + dy^2) + dz^2, and
+ *   acos((double)dot) < eps_angle, dot the float ((n_i.x n_j.x + n_i.y n_j.y) + n_i.z n_j.z);
+ * a NaN anywhere, or dot > 1 (acos is NaN), gives no edge.  A component of at least min_points points
+ * is a cluster; the clusters are numbered by their lowest index.  labels: n int32, the point's
+ * cluster or -1; *n_clusters: their number.  DESIGN.md "CVFH: the contract" states every operation;
+ * the CPU restatement of that text is the truth the kernels are tested against (parity with PCL
+ * itself is unpinned).  Nothing is kept per point but a parent word: there is no capacity.
+ * A null required pointer, a negative size, a NaN or non-positive tolerance, a NaN eps_angle,
+ * min_points < 1 or n >= 2^31: PFX_ERR_INVALID before anything is copied or launched.  n == 0 gives
+ * no cluster.  Statistics: "cvfh_edges" (the edges, each once), "cvfh_cc_rounds" (hooking rounds,
+ * the last one, which changes nothing, included), "cvfh_clusters". */
+pfx_status pfx_smooth_clusters(pfx_ctx* ctx, const float* x, const float* y, const float* z, const float* nx,
+                               const float* ny, const float* nz, int64_t n, float tolerance, double eps_angle,
+                               int32_t min_points, int32_t* labels, int64_t* n_clusters);
+/* Device pointers (d_n_clusters too), on the ctx stream.  The call waits on the host once, for the
+ * flag that says the components are complete (and again for every 8 hooking rounds beyond the
+ * first 8); the statistics are set when it returns. */
+pfx_status pfx_smooth_clusters_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z,
+                                   const float* d_nx, const float* d_ny, const float* d_nz, int64_t n,
+                                   float tolerance, double eps_angle, int32_t min_points, int32_t* d_labels,
+                                   int64_t* d_n_clusters);
+
+/* PCL 1.7's defaults (pfx_cvfh_params_default): viewpoint (0, 0, 0), radius_normals and
+ * cluster_tolerance 3 * 0.005f (leaf_size_ * 3), eps_angle_threshold 0.125f, curvature_threshold
+ * 0.03f, min_points 50, normalize_bins 0. */
+typedef struct pfx_cvfh_params {
+  float viewpoint[3];
+  float radius_normals;
+  float cluster_tolerance;
+  float eps_angle_threshold;
+  float curvature_threshold;
+  int32_t min_points;
+  int32_t normalize_bins;
+} pfx_cvfh_params;
+void pfx_cvfh_params_default(pfx_cvfh_params* p);
+
+#define PFX_CVFH_DIM 308
+/* CVFH over the n_indices points indices[0..) of the surface (indices == NULL: all n_surface points,
+ * and n_indices must equal n_surface): the points whose curvature is not above the threshold are
+ * given new normals (pfx_normals at radius_normals, viewpoint (0, 0, 0)) and clustered
+ * (pfx_smooth_clusters); every cluster gives one row, a VFH signature of ALL indexed points about
+ * the cluster's mean point and normalised mean normal: 45 bins each of f1, f2, f3 and f4, then 128 of
+ * the viewpoint component.  Without a cluster there is one row, about the centroid of the whole
+ * surface and the mean of the indexed normals.  Every bin is the float sum of a count of equal
+ * increments, so a row is a function of integer counts; nothing depends on the order of execution.
+ *   out               cap x 308 floats; *n_rows the number of rows
+ *   centroids         (nullable) cap x 3, dominant_normals (nullable) cap x 3: what each row is about
+ *   labels            (nullable) n_indices int32: the indexed point's cluster, or -1
+ * More rows than cap: PFX_ERR_CAPACITY with the required number in *n_rows and nothing written.
+ * n_indices > 2^24 (a float stops counting exactly): PFX_ERR_CAPACITY.  n_indices == 0: no row.
+ * An index outside [0, n_surface), a null required pointer, a negative size, a NaN or non-positive
+ * radius_normals or cluster_tolerance, a NaN eps_angle_threshold, min_points < 1: PFX_ERR_INVALID.
+ * Statistics: "cvfh_filtered" (the points that pass the curvature filter), "cvfh_clusters",
+ * "cvfh_edges", "cvfh_cc_rounds", "cvfh_rows". */
+pfx_status pfx_cvfh(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
+                    const float* sny, const float* snz, const float* scurvature, int64_t n_surface,
+                    const int32_t* indices, int64_t n_indices, const pfx_cvfh_params* params, float* out, int64_t cap,
+                    int64_t* n_rows, float* centroids, float* dominant_normals, int32_t* labels);
+/* Device pointers (d_n_rows too), on the ctx stream.  The call waits on the host as pfx_normals_dev
+ * does for its lists and then once for the cluster count (and as pfx_smooth_clusters_dev says beyond
+ * 8 rounds); the capacity and index errors are returned by the call itself and the statistics are
+ * set when it returns.  The rows are complete in stream order. */
+pfx_status pfx_cvfh_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz, const float* d_snx,
+                        const float* d_sny, const float* d_snz, const float* d_scurvature, int64_t n_surface,
+                        const int32_t* d_indices, int64_t n_indices, const pfx_cvfh_params* params, float* d_out,
+                        int64_t cap, int64_t* d_n_rows, float* d_centroids, float* d_dominant_normals,
+                        int32_t* d_labels);
 
 /* ---- range image + NARF keypoints ---------------------------------------------------- */
 /* out_points: width*height x 4 floats {x, y, z, range} (PointWithRange); unobserved pixels

@@ -229,6 +229,8 @@ struct ReferenceFrame { float x_axis[3], y_axis[3], z_axis[3]; };
 struct Boundary { uint8_t boundary_point = 0; };
 static_assert(sizeof(Boundary) == 1, "pcl::Boundary is one byte");
 // (PCL's Narf36: the patch's position and orientation in the world, then the descriptor)
+// pcl::VFHSignature308: CVFH's row (45 bins each of f1, f2, f3, f4, then 128 of the viewpoint component)
+struct VFHSignature308 { float histogram[308]; };
 struct Narf36 { float x = 0, y = 0, z = 0, roll = 0, pitch = 0, yaw = 0; float descriptor[36] = {}; };
 static_assert(sizeof(Narf36) == 42 * sizeof(float), "pcl::Narf36 is 42 floats");
 
@@ -1005,6 +1007,75 @@ class BoundaryEstimation : public FeatureFromNormals<PointInT, PointNT, PointOut
   float angle_threshold_ = static_cast<float>(M_PI) / 2.0f;
 };
 
+// CVFHEstimation<In, Normal, VFHSignature308> (evaluation.cpp:649-675): the rows of pfx_cvfh, one per
+// smooth cluster, or one row without a cluster.  A FeatureFromNormals, so the generic wrapper
+// (features.h:181-187) estimates the cloud's normals, curvature included.  Two things PCL 1.7 does on
+// this path are reproduced:
+//   the wrapper calls compute on the Feature base, so Feature::compute runs and CVFH's own compute,
+//   which hides it, does not; computeFeature sizes the output to the number of rows;
+//   the wrapper sets the cloud as the search surface and the keypoints as the input, so the indices
+//   are 0 .. K - 1 and CVFH reads the surface's points and normals at them: it describes the FIRST K
+//   POINTS OF THE CLOUD, not the keypoints.  More keypoints than surface points, which PCL would read
+//   out of bounds, is PFX_ERR_INVALID.
+// The constructor sets k = 1 and no radius, as PCL's: with a radius set, compute() fails as PCL's
+// initCompute does until setKSearch(0).  The lists getCentroidClusters / getCentroidNormalClusters
+// return are cleared by every compute (PCL 1.7 clears only the first).
+template <typename PointInT, typename PointNT, typename PointOutT = VFHSignature308>
+class CVFHEstimation : public FeatureFromNormals<PointInT, PointNT, PointOutT> {
+ public:
+  typedef std::shared_ptr<CVFHEstimation<PointInT, PointNT, PointOutT> > Ptr;
+  typedef std::shared_ptr<const CVFHEstimation<PointInT, PointNT, PointOutT> > ConstPtr;
+  CVFHEstimation() {
+    this->name_ = "CVFHEstimation";
+    this->k_ = 1;
+    this->search_radius_ = 0.0;
+    this->k_search_error_ = "[pcl::CVFHEstimation::initCompute] Both radius and K defined! Set one of them to zero "
+                            "first and then re-run compute ().";
+    pfx_cvfh_params_default(&prm_);
+  }
+  void setViewPoint(float vpx, float vpy, float vpz) { prm_.viewpoint[0] = vpx; prm_.viewpoint[1] = vpy; prm_.viewpoint[2] = vpz; }
+  void getViewPoint(float& vpx, float& vpy, float& vpz) const { vpx = prm_.viewpoint[0]; vpy = prm_.viewpoint[1]; vpz = prm_.viewpoint[2]; }
+  void setRadiusNormals(float radius_normals) { prm_.radius_normals = radius_normals; }
+  void setClusterTolerance(float d) { prm_.cluster_tolerance = d; }
+  void setEPSAngleThreshold(float d) { prm_.eps_angle_threshold = d; }
+  void setCurvatureThreshold(float d) { prm_.curvature_threshold = d; }
+  void setMinPoints(size_t min) { prm_.min_points = (int32_t)min; }
+  void setNormalizeBins(bool normalize) { prm_.normalize_bins = normalize ? 1 : 0; }
+  void getCentroidClusters(std::vector<Eigen::Vector3f>& centroids) const {
+    for (const Eigen::Vector3f& c : centroids_) centroids.push_back(c);
+  }
+  void getCentroidNormalClusters(std::vector<Eigen::Vector3f>& centroids) const {
+    for (const Eigen::Vector3f& c : dominant_normals_) centroids.push_back(c);
+  }
+
+ protected:
+  void computeFeature(PointCloud<PointOutT>& out) override {
+    centroids_.clear();
+    dominant_normals_.clear();
+    if (!this->normals_match("the input normals are missing or do not match the search surface")) return;
+    const detail::SoA s = detail::soa_xyz(this->surface()), nrm = detail::soa_normals(*this->normals_);
+    std::vector<float> curv(s.size());
+    for (size_t i = 0; i < curv.size(); ++i) curv[i] = this->normals_->points[i].curvature;
+    std::vector<int32_t> indices(this->input_->size());  // Feature::initCompute's: 0 .. K - 1
+    for (size_t i = 0; i < indices.size(); ++i) indices[i] = (int32_t)i;
+    const int64_t cap = std::max<int64_t>(1, (int64_t)indices.size() / std::max<int32_t>(1, prm_.min_points));
+    std::vector<float> rows((size_t)cap * PFX_CVFH_DIM), cen((size_t)cap * 3), dn((size_t)cap * 3);
+    int64_t n_rows = 0;
+    if (!detail::ok(pfx_cvfh(detail::context(), s.x.data(), s.y.data(), s.z.data(), nrm.x.data(), nrm.y.data(),
+                             nrm.z.data(), curv.data(), s.n(), indices.data(), (int64_t)indices.size(), &prm_,
+                             rows.data(), cap, &n_rows, cen.data(), dn.data(), nullptr),
+                    "CVFHEstimation"))
+      return;
+    detail::write_rows<PFX_CVFH_DIM>(out, (size_t)n_rows, detail::NanRule::kFirstFloat, rows);
+    for (int64_t r = 0; r < n_rows; ++r) {
+      centroids_.push_back(Eigen::Vector3f(cen[r * 3], cen[r * 3 + 1], cen[r * 3 + 2]));
+      dominant_normals_.push_back(Eigen::Vector3f(dn[r * 3], dn[r * 3 + 1], dn[r * 3 + 2]));
+    }
+  }
+  pfx_cvfh_params prm_;
+  std::vector<Eigen::Vector3f> centroids_, dominant_normals_;
+};
+
 // UniqueShapeContext<In, ShapeContext1980, ReferenceFrame>.  Without input frames it computes them
 // with SHOTLocalReferenceFrameEstimation at the local radius (PCL's default: 2.5) over the search
 // surface.  That frame search has SHOT's capacity, 16,384 neighbours: on a cloud where the local
@@ -1484,6 +1555,7 @@ template <> struct DescriptorLayout<SHOT352> { static constexpr int dim = 352, s
 template <> struct DescriptorLayout<SHOT1344> { static constexpr int dim = 1344, stride = 1353; };
 template <> struct DescriptorLayout<ShapeContext1980> { static constexpr int dim = 1980, stride = 1989; };
 template <> struct DescriptorLayout<PFHSignature125> { static constexpr int dim = 125, stride = 125; };
+template <> struct DescriptorLayout<VFHSignature308> { static constexpr int dim = 308, stride = 308; };
 template <int N> struct DescriptorLayout<Histogram<N> > { static constexpr int dim = N, stride = N; };
 // (DefaultPointRepresentation<IntensityGradient>: the three gradient floats of a 16-byte point)
 template <> struct DescriptorLayout<IntensityGradient> { static constexpr int dim = 3, stride = 4; };

@@ -108,6 +108,19 @@ class NarfDescParams(ctypes.Structure):
     ]
 
 
+class CvfhParams(ctypes.Structure):
+    """pfx_cvfh_params (CVFHEstimation's setters)."""
+    _fields_ = [
+        ("viewpoint", ctypes.c_float * 3),
+        ("radius_normals", ctypes.c_float),
+        ("cluster_tolerance", ctypes.c_float),
+        ("eps_angle_threshold", ctypes.c_float),
+        ("curvature_threshold", ctypes.c_float),
+        ("min_points", ctypes.c_int32),
+        ("normalize_bins", ctypes.c_int32),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "pfx_narf_params_default": (None, [ctypes.POINTER(NarfParams)]),
@@ -193,6 +206,14 @@ _SIGS = {
                              ctypes.c_float, c_vp]),
     "pfx_boundary_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_dbl,
                                  ctypes.c_float, c_vp]),
+    "pfx_smooth_clusters": (c_int, [c_vp] + [c_vp] * 6 + [c_i64, ctypes.c_float, c_dbl, ctypes.c_int32, c_vp, c_vp]),
+    "pfx_smooth_clusters_dev": (c_int, [c_vp] + [c_vp] * 6 + [c_i64, ctypes.c_float, c_dbl, ctypes.c_int32, c_vp,
+                                                              c_vp]),
+    "pfx_cvfh_params_default": (None, [ctypes.POINTER(CvfhParams)]),
+    "pfx_cvfh": (c_int, [c_vp] + [c_vp] * 7 + [c_i64, c_vp, c_i64, ctypes.POINTER(CvfhParams), c_vp, c_i64, c_vp, c_vp,
+                                               c_vp, c_vp]),
+    "pfx_cvfh_dev": (c_int, [c_vp] + [c_vp] * 7 + [c_i64, c_vp, c_i64, ctypes.POINTER(CvfhParams), c_vp, c_i64, c_vp,
+                                                   c_vp, c_vp, c_vp]),
     "pfx_shape_context": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
                                   c_dbl, c_dbl, c_vp, c_vp, c_vp]),
     "pfx_shape_context_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_dbl,
@@ -278,7 +299,9 @@ _OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_i
                    "pfx_principal_curvatures", "pfx_principal_curvatures_dev",
                    "pfx_board_params_default", "pfx_board_lrf", "pfx_board_lrf_dev",
                    "pfx_boundary", "pfx_boundary_dev", "pfx_narf_desc_params_default", "pfx_narf_descriptors",
-                   "pfx_narf_descriptors_dev", "pfx_point_indices", "pfx_point_indices_dev"}
+                   "pfx_narf_descriptors_dev", "pfx_point_indices", "pfx_point_indices_dev",
+                   "pfx_smooth_clusters", "pfx_smooth_clusters_dev", "pfx_cvfh_params_default", "pfx_cvfh",
+                   "pfx_cvfh_dev"}
 
 _lib = None
 

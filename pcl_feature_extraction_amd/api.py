@@ -94,6 +94,23 @@ def board_params(tangent_radius=0.0, margin_thresh=0.85, find_holes=False) -> N.
     return p
 
 
+def cvfh_params(viewpoint=(0.0, 0.0, 0.0), radius_normals=None, cluster_tolerance=None, eps_angle_threshold=None,
+                curvature_threshold=None, min_points=None, normalize_bins=False) -> N.CvfhParams:
+    """pfx_cvfh_params; what is left None keeps PCL's default (pfx_cvfh_params_default: 0.015f, 0.015f,
+    0.125f, 0.03f, 50)."""
+    p = N.CvfhParams()
+    N.lib().pfx_cvfh_params_default(ctypes.byref(p))
+    p.viewpoint[0], p.viewpoint[1], p.viewpoint[2] = map(float, viewpoint)
+    for k, v in (("radius_normals", radius_normals), ("cluster_tolerance", cluster_tolerance),
+                 ("eps_angle_threshold", eps_angle_threshold), ("curvature_threshold", curvature_threshold)):
+        if v is not None:
+            setattr(p, k, float(v))
+    if min_points is not None:
+        p.min_points = int(min_points)
+    p.normalize_bins = int(bool(normalize_bins))
+    return p
+
+
 def rgb_to_intensity(rgb) -> np.ndarray:
     """pcl::PointXYZRGBtoXYZI on packed 0x00RRGGBB words: (0.299f * r + 0.587f * g) + 0.114f * b,
     every step in float32.  Input preparation for Context.intensity_gradient, not a feature."""
@@ -107,6 +124,10 @@ def rgb_to_intensity(rgb) -> np.ndarray:
 #: result of Context.narf_descriptors: desc (m, 36), pose (m, 12) the row-major 3 x 4 world -> patch
 #: transforms, keypoint (m,) the entry of pixel_idx each row came from
 NarfDescriptors = collections.namedtuple("NarfDescriptors", "desc pose keypoint")
+
+#: result of Context.cvfh: rows (m, 308), centroids (m, 3) and dominant_normals (m, 3) what each row is
+#: about, labels (n_indices,) the indexed point's cluster or -1
+Cvfh = collections.namedtuple("Cvfh", "rows centroids dominant_normals labels")
 
 #: result of Context.icp / icp_dev; state: 0 not converged, 1 iterations, 2 transform, 3 absolute
 #: MSE, 4 relative MSE, 5 no correspondences (pfx.h PFX_ICP_*); aligned: (x, y, z) or None
@@ -448,6 +469,42 @@ class Context:
                                            float(angle_threshold), _ptr(out)))
         return out
 
+    def smooth_clusters(self, x, y, z, nx, ny, nz, tolerance, eps_angle, min_points):
+        """extractEuclideanClustersSmooth (pfx_smooth_clusters): (labels (n,) int32, n_clusters).  A label
+        is the point's cluster, numbered by the clusters' lowest index, or -1."""
+        x, y, z, nx, ny, nz = map(_f32, (x, y, z, nx, ny, nz))
+        if not len(x) == len(y) == len(z) == len(nx) == len(ny) == len(nz):
+            raise ValueError("smooth_clusters: one normal per point")
+        labels, n_out = np.empty(len(x), np.int32), np.zeros(1, np.int64)
+        self._check(self._lib.pfx_smooth_clusters(self.h, _ptr(x), _ptr(y), _ptr(z), _ptr(nx), _ptr(ny), _ptr(nz),
+                                                  len(x), float(tolerance), float(eps_angle), int(min_points),
+                                                  _ptr(labels), _ptr(n_out)))
+        return labels, int(n_out[0])
+
+    def cvfh(self, sx, sy, sz, snx, sny, snz, scurvature, indices=None, params=None, cap=None):
+        """CVFHEstimation (pfx_cvfh) over the surface points `indices` (None: all): Cvfh(rows, centroids,
+        dominant_normals, labels), one row per smooth cluster, or one row when there is none.  cap (None:
+        as many as can arise): fewer than the rows is PFX_ERR_CAPACITY."""
+        params = params or cvfh_params()
+        sx, sy, sz, snx, sny, snz, scurvature = map(_f32, (sx, sy, sz, snx, sny, snz, scurvature))
+        if not len(sx) == len(sy) == len(sz) == len(snx) == len(sny) == len(snz) == len(scurvature):
+            raise ValueError("cvfh: one normal and one curvature per surface point")
+        idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.int32)
+        n_idx = len(sx) if idx is None else len(idx)
+        if cap is None:
+            cap = max(1, n_idx // max(1, params.min_points))
+        rows, cen, dn = (np.empty((cap, w), np.float32) for w in (308, 3, 3))
+        labels, n_out = np.empty(n_idx, np.int32), np.zeros(1, np.int64)
+        try:
+            self._check(self._lib.pfx_cvfh(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(snx), _ptr(sny), _ptr(snz),
+                                           _ptr(scurvature), len(sx), _ptr(idx), n_idx, ctypes.byref(params),
+                                           _ptr(rows), cap, _ptr(n_out), _ptr(cen), _ptr(dn), _ptr(labels)))
+        except N.PfxError as e:
+            e.required = int(n_out[0])  # (PFX_ERR_CAPACITY: the rows the call needs)
+            raise
+        m = int(n_out[0])
+        return Cvfh(rows[:m].copy(), cen[:m].copy(), dn[:m].copy(), labels)
+
     def range_image_planar(self, x, y, z, cam=None):
         cam = cam or camera()
         x, y, z = map(_f32, (x, y, z))
@@ -733,6 +790,26 @@ class Context:
         self._check(self._lib.pfx_boundary_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), sx.numel(), _ptr(qx), _ptr(qy),
                                                _ptr(qz), _ptr(qnx), _ptr(qny), _ptr(qnz), qx.numel(), float(r),
                                                float(angle_threshold), _ptr(out)))
+
+    def smooth_clusters_dev(self, x, y, z, nx, ny, nz, tolerance, eps_angle, min_points, labels, n_clusters):
+        """pfx_smooth_clusters_dev: labels an (n,) int32 and n_clusters a (1,) int64 device tensor.  Waits
+        on the host for the components to be complete; the statistics are set when it returns."""
+        self._check(self._lib.pfx_smooth_clusters_dev(self.h, _ptr(x), _ptr(y), _ptr(z), _ptr(nx), _ptr(ny), _ptr(nz),
+                                                      x.numel(), float(tolerance), float(eps_angle), int(min_points),
+                                                      _ptr(labels), _ptr(n_clusters)))
+
+    def cvfh_dev(self, sx, sy, sz, snx, sny, snz, scurvature, indices, out, n_rows, params=None, centroids=None,
+                 dominant_normals=None, labels=None):
+        """pfx_cvfh_dev: out a (cap, 308) float32, n_rows a (1,) int64 device tensor; indices an int32
+        device tensor or None; centroids / dominant_normals (cap, 3) and labels (n_indices,) int32 or
+        None.  Waits on the host for the cluster count; more rows than cap raises PFX_ERR_CAPACITY with
+        the required count in n_rows."""
+        params = params or cvfh_params()
+        n_idx = sx.numel() if indices is None else indices.numel()
+        self._check(self._lib.pfx_cvfh_dev(self.h, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(snx), _ptr(sny), _ptr(snz),
+                                           _ptr(scurvature), sx.numel(), _ptr(indices), n_idx, ctypes.byref(params),
+                                           _ptr(out), out.shape[0], _ptr(n_rows), _ptr(centroids),
+                                           _ptr(dominant_normals), _ptr(labels)))
 
     def narf_keypoints_dev(self, x, y, z, params=None, cam=None, cap=1 << 20):
         cam = cam or camera()

@@ -1021,6 +1021,131 @@ pfx_status pfx_boundary(pfx_ctx* ctx, const float* sx, const float* sy, const fl
   PFX_API_END(ctx)
 }
 
+// The points are the surface side of the one argument rule; there is no query side.
+static void smooth_clusters_rule(In3 p, In3 nrm, int64_t n, float tolerance, double eps_angle, int32_t min_points,
+                                 const int32_t* labels, const int64_t* n_clusters) {
+  args_rule("smooth_clusters", n, all_set(p, nrm, labels), 0, true, n_clusters != nullptr);
+  if (!(tolerance > 0.0f)) throw Error(PFX_ERR_INVALID, "smooth_clusters: the tolerance must be > 0");
+  if (std::isnan(eps_angle)) throw Error(PFX_ERR_INVALID, "smooth_clusters: eps_angle is NaN");
+  if (min_points < 1) throw Error(PFX_ERR_INVALID, "smooth_clusters: min_points must be >= 1");
+  if (n >= (int64_t(1) << 31)) throw Error(PFX_ERR_INVALID, "smooth_clusters: 2^31 points or more");
+}
+
+pfx_status pfx_smooth_clusters_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z,
+                                   const float* d_nx, const float* d_ny, const float* d_nz, int64_t n,
+                                   float tolerance, double eps_angle, int32_t min_points, int32_t* d_labels,
+                                   int64_t* d_n_clusters) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  smooth_clusters_rule({d_x, d_y, d_z}, {d_nx, d_ny, d_nz}, n, tolerance, eps_angle, min_points, d_labels,
+                       d_n_clusters);
+  pfx::smooth_clusters_dev(ctx, d_x, d_y, d_z, d_nx, d_ny, d_nz, n, tolerance, eps_angle, min_points, d_labels,
+                           d_n_clusters);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_smooth_clusters(pfx_ctx* ctx, const float* x, const float* y, const float* z, const float* nx,
+                               const float* ny, const float* nz, int64_t n, float tolerance, double eps_angle,
+                               int32_t min_points, int32_t* labels, int64_t* n_clusters) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  smooth_clusters_rule({x, y, z}, {nx, ny, nz}, n, tolerance, eps_angle, min_points, labels, n_clusters);
+  const Dev3 p = stage3(ctx, "in_", x, y, z, n), a = stage3(ctx, "in_n", nx, ny, nz, n);
+  int32_t* dlab = ctx->buf("out_labels").as<int32_t>(n + 1);
+  int64_t* dn = ctx->buf("out_count").as<int64_t>(1);
+  pfx::smooth_clusters_dev(ctx, p.x, p.y, p.z, a.x, a.y, a.z, n, tolerance, eps_angle, min_points, dlab, dn);
+  PFX_HIP(hipMemcpyAsync(n_clusters, dn, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  finish_host(ctx, n, {{labels, (const int32_t*)dlab, 1}});
+  PFX_API_END(ctx)
+}
+
+void pfx_cvfh_params_default(pfx_cvfh_params* p) {
+  if (!p) return;
+  const float leaf_size = 0.005f;
+  p->viewpoint[0] = p->viewpoint[1] = p->viewpoint[2] = 0.0f;
+  p->radius_normals = leaf_size * 3;
+  p->cluster_tolerance = leaf_size * 3;
+  p->eps_angle_threshold = 0.125f;
+  p->curvature_threshold = 0.03f;
+  p->min_points = 50;
+  p->normalize_bins = 0;
+}
+
+// The surface is the surface side and the indices the query side of the one argument rule (NULL
+// indices: every surface point, so the counts must agree); the outputs are needed where cap allows a
+// row.  Then the family's own rules, with their own texts.
+static void cvfh_rule(In3 s, In3 nrm, const float* curv, int64_t n_surface, const int32_t* indices, int64_t n_indices,
+                      const pfx_cvfh_params* p, const float* out, int64_t cap, const int64_t* n_rows) {
+  args_rule("cvfh", n_surface, all_set(s, nrm, curv), n_indices, true,
+            p && n_rows && cap >= 0 && (cap == 0 || out) && (indices || n_indices == n_surface) &&
+                (n_indices == 0 || n_surface > 0) && n_surface < (int64_t(1) << 31));
+  if (!(p->radius_normals > 0.0f)) throw Error(PFX_ERR_INVALID, "cvfh: radius_normals must be > 0");
+  if (!(p->cluster_tolerance > 0.0f)) throw Error(PFX_ERR_INVALID, "cvfh: cluster_tolerance must be > 0");
+  if (std::isnan(p->eps_angle_threshold)) throw Error(PFX_ERR_INVALID, "cvfh: eps_angle_threshold is NaN");
+  if (p->min_points < 1) throw Error(PFX_ERR_INVALID, "cvfh: min_points must be >= 1");
+  if (n_indices > (int64_t(1) << 24))
+    throw Error(PFX_ERR_CAPACITY, "cvfh: more than 2^24 indexed points (a float bin stops counting exactly)");
+}
+
+pfx_status pfx_cvfh_dev(pfx_ctx* ctx, const float* d_sx, const float* d_sy, const float* d_sz, const float* d_snx,
+                        const float* d_sny, const float* d_snz, const float* d_scurvature, int64_t n_surface,
+                        const int32_t* d_indices, int64_t n_indices, const pfx_cvfh_params* params, float* d_out,
+                        int64_t cap, int64_t* d_n_rows, float* d_centroids, float* d_dominant_normals,
+                        int32_t* d_labels) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  cvfh_rule({d_sx, d_sy, d_sz}, {d_snx, d_sny, d_snz}, d_scurvature, n_surface, d_indices, n_indices, params, d_out,
+            cap, d_n_rows);
+  pfx::cvfh_dev(ctx, d_sx, d_sy, d_sz, d_snx, d_sny, d_snz, d_scurvature, n_surface, d_indices, n_indices, *params,
+                d_out, cap, d_n_rows, d_centroids, d_dominant_normals, d_labels);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_cvfh(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx,
+                    const float* sny, const float* snz, const float* scurvature, int64_t n_surface,
+                    const int32_t* indices, int64_t n_indices, const pfx_cvfh_params* params, float* out, int64_t cap,
+                    int64_t* n_rows, float* centroids, float* dominant_normals, int32_t* labels) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  cvfh_rule({sx, sy, sz}, {snx, sny, snz}, scurvature, n_surface, indices, n_indices, params, out, cap, n_rows);
+  *n_rows = 0;
+  if (n_indices) {  // (without points nothing is staged or run)
+    if (indices)  // (checked here, before anything is copied; the device form checks in its filter)
+      for (int64_t i = 0; i < n_indices; ++i)
+        if (indices[i] < 0 || indices[i] >= n_surface)
+          throw Error(PFX_ERR_INVALID, "cvfh: an index is outside the surface");
+    const Dev3 s = stage3(ctx, "in_", sx, sy, sz, n_surface), a = stage3(ctx, "in_n", snx, sny, snz, n_surface);
+    const float* dcurv = stage_in(ctx, "in_curv", scurvature, n_surface);
+    int32_t* didx = nullptr;
+    if (indices) {
+      didx = ctx->buf("in_indices").as<int32_t>(n_indices);
+      PFX_HIP(hipMemcpyAsync(didx, indices, sizeof(int32_t) * n_indices, hipMemcpyHostToDevice, ctx->stream));
+    }
+    // (a cluster has min_points points or more of the n_indices)
+    const int64_t room = std::min<int64_t>(cap, std::max<int64_t>(1, n_indices / params->min_points));
+    float* dout = ctx->buf("out_cvfh").as<float>(room * (PFX_CVFH_DIM + 6) + 1);
+    float *dcen = dout + room * PFX_CVFH_DIM, *ddn = dcen + room * 3;
+    int32_t* dlab = ctx->buf("out_labels").as<int32_t>(n_indices + 1);
+    int64_t* dn = ctx->buf("out_count").as<int64_t>(1);
+    try {
+      *n_rows = pfx::cvfh_dev(ctx, s.x, s.y, s.z, a.x, a.y, a.z, dcurv, n_surface, didx, n_indices, *params, dout,
+                              room, dn, dcen, ddn, dlab);
+    } catch (const Error& e) {
+      if (e.code != PFX_ERR_CAPACITY) throw;
+      PFX_HIP(hipMemcpyAsync(n_rows, dn, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+      PFX_HIP(hipStreamSynchronize(ctx->stream));
+      throw;
+    }
+    rows_out(ctx, labels, (const int32_t*)dlab, n_indices, 1);
+    finish_host(ctx, *n_rows, {{out, (const float*)dout, PFX_CVFH_DIM}, {centroids, (const float*)dcen, 3},
+                               {dominant_normals, (const float*)ddn, 3}});
+  } else {
+    for (const char* st : {"cvfh_filtered", "cvfh_clusters", "cvfh_edges", "cvfh_cc_rounds", "cvfh_rows"})
+      ctx->stats[st] = 0;
+  }
+  PFX_API_END(ctx)
+}
+
 // Both shape contexts' rule.  `normals_set`: the 3DSC needs the surface normals, the USC has none;
 // `frames_set`: the USC needs the frames, the 3DSC has none.
 static void sc_rule(const char* what, In3 s, bool normals_set, int64_t n_surface, In3 q, bool frames_set, int64_t nq,

@@ -464,6 +464,16 @@ int board_cap_small();
 void boundary_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, int64_t ns, const float* qx,
                   const float* qy, const float* qz, const float* qnx, const float* qny, const float* qnz, int64_t nq,
                   double r, float angle_threshold, uint8_t* out);
+// smooth clusters and CVFH (pfx_cvfh.hip).  Both wait on the host (pfx.h says when) and set their
+// statistics before they return.  cvfh_dev returns the number of rows; more than cap: the required
+// number is written to *d_n_rows and PFX_ERR_CAPACITY thrown.
+void smooth_clusters_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, const float* nx,
+                         const float* ny, const float* nz, int64_t n, float tolerance, double eps_angle,
+                         int32_t min_points, int32_t* labels, int64_t* d_n_clusters);
+int64_t cvfh_dev(pfx_ctx* ctx, const float* sx, const float* sy, const float* sz, const float* snx, const float* sny,
+                 const float* snz, const float* scurv, int64_t ns, const int32_t* indices, int64_t np,
+                 const pfx_cvfh_params& prm, float* out, int64_t cap, int64_t* d_n_rows, float* centroids,
+                 float* dominant_normals, int32_t* labels);
 // boost::mt19937 through uniform_01<float>: n floats of the stream of `seed` after `skip` floats
 void rng_uniform01(uint32_t seed, int64_t skip, int64_t n, float* out);
 void range_image_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
