@@ -64,6 +64,8 @@
  *   pfx_cloud_resolution* <- Keypoints::computeCloudResolution (keypoints.h:401-428)
  *   pfx_iss_keypoints*  <- ISSKeypoint3D<PointXYZRGB,PointXYZRGB>::compute as configured by
  *                          Keypoints::compute's ISS branch (keypoints.h:177-189)
+ *   pfx_uniform_sampling* <- UniformSampling<PointXYZRGB>::compute as Keypoints::compute's
+ *                          UNIFORM_SAMPLING branch configures it (keypoints.h:274-290)
  *   pfx_harris3d_keypoints* <- HarrisKeypoint3D<PointXYZRGB,PointXYZI>::compute + getKeypointsCloud
  *   pfx_harris6d_keypoints* <- HarrisKeypoint6D<PointXYZRGB,PointXYZI>::compute + getKeypointsCloud
  *                          (Keypoints::compute's HARRIS_3D branch, keypoints.h:150-162, 365-395)
@@ -997,6 +999,28 @@ pfx_status pfx_iss_keypoints(pfx_ctx* ctx, const float* x, const float* y, const
                              double salient_radius, double non_max_radius, int32_t min_neighbors,
                              double threshold21, double threshold32, int32_t* idx, int64_t cap, int64_t* n_out,
                              double* third);
+
+/* UniformSampling::compute (PCL 1.7 keypoints/impl/uniform_sampling.hpp) with setRadiusSearch(radius):
+ * one keypoint per occupied voxel of edge leaf = (float)radius, by DESIGN.md "Uniform sampling: the
+ * contract".  A point with a non-finite coordinate takes no part.  The cell of a point is
+ * (int)floorf(coordinate * inv), inv = 1.0f / leaf; its winner is the point with the smallest
+ * (diff, index), diff = (dx*dx + dz*dz) + (dy*dy + 1.0f) in float32 with dx = x - (float)i, ...:
+ * PCL subtracts the integer cell coordinates, not the cell's centre.  idx[0..cap) receives the
+ * winners' cloud indices in ascending leaf index (PCL: the iteration order of a
+ * boost::unordered_map, the same set), leaf (nullable, cap) each keypoint's leaf index
+ * (i - min_i) + (j - min_j) div_x + (k - min_k) div_x div_y, *n_out the number of occupied cells;
+ * 0 for n == 0 or a cloud without a finite point.
+ *   PFX_ERR_INVALID   unless leaf is finite and > 0 and inv is finite (radius 0, negative, NaN, 1e-46);
+ *   PFX_ERR_CAPACITY  nothing written: *n_out exceeds cap (*n_out = the required count); or a product
+ *                     coordinate * inv lies outside [-2^31, 2^31), or the bounding box holds more than
+ *                     2^31 - 1 cells (*n_out = 0; PCL's int leaf index overflows silently there).
+ * There is no other limit on the extent: memory grows with n, never with the number of cells.  Two
+ * host waits (the bounds, the count).  Statistics: "uniform_points" (the points that took part),
+ * "uniform_leaves" (*n_out), "uniform_cells" (div_x div_y div_z). */
+pfx_status pfx_uniform_sampling_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z, int64_t n,
+                                    double radius, int32_t* d_idx, int64_t cap, int64_t* n_out, int32_t* d_leaf);
+pfx_status pfx_uniform_sampling(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
+                                double radius, int32_t* idx, int64_t cap, int64_t* n_out, int32_t* leaf);
 
 /* HarrisKeypoint3D (method HARRIS) + Keypoints::getKeypointsCloud: response over the normals of
  * the radius ball (NormalEstimation at the same radius, viewpoint 0), non-maximum suppression

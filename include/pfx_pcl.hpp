@@ -1409,6 +1409,52 @@ class ISSKeypoint3D {
   std::vector<int> indices_;
 };
 
+// ---- UniformSampling (keypoints.h:274-290) -----------------------------------------------------
+// UniformSampling<In>: setRadiusSearch, setInputCloud, compute(PointCloud<int>&) -> the cloud
+// indices of one keypoint per occupied voxel (pfx_uniform_sampling), in ascending leaf index where
+// PCL emits them in the iteration order of a boost::unordered_map (the same set; DESIGN.md "Uniform
+// sampling: the contract").  setSearchMethod is accepted and unused: PCL builds a tree it never
+// queries.  No radius set, no input, or a status other than success (a radius PCL's leaf size
+// cannot take, more cells than an int indexes) -> PCL_ERROR and an empty output.
+template <typename PointInT>
+class UniformSampling {
+ public:
+  typedef typename PointCloud<PointInT>::ConstPtr PointCloudInConstPtr;
+  typedef typename search::KdTree<PointInT>::Ptr KdTreePtr;
+  void setInputCloud(const PointCloudInConstPtr& cloud) { input_ = cloud; }
+  void setSearchMethod(const KdTreePtr& tree) { tree_ = tree; }
+  void setRadiusSearch(double radius) { search_radius_ = radius; }
+  double getRadiusSearch() const { return search_radius_; }
+  void compute(PointCloud<int>& output) {
+    output.clear();
+    output.is_dense = true;
+    if (!input_) {
+      PCL_ERROR("[pcl::UniformSampling::compute] no input cloud\n");
+      return;
+    }
+    if (search_radius_ == 0.0) {
+      PCL_ERROR("[pcl::UniformSampling::compute] no radius set (setRadiusSearch)\n");
+      return;
+    }
+    if (!detail::context()) return;
+    const detail::SoA c = detail::soa_xyz(*input_);
+    std::vector<int32_t> idx(c.size() + 1);
+    int64_t k = 0;
+    if (!detail::ok(pfx_uniform_sampling(detail::context(), c.x.data(), c.y.data(), c.z.data(), c.n(), search_radius_,
+                                         idx.data(), (int64_t)idx.size(), &k, nullptr),
+                    "UniformSampling"))
+      return;
+    output.points.assign(idx.begin(), idx.begin() + k);
+    output.width = (uint32_t)k;
+    output.height = 1;
+  }
+
+ private:
+  PointCloudInConstPtr input_;
+  KdTreePtr tree_;
+  double search_radius_ = 0.0;
+};
+
 // Keypoints::computeCloudResolution (keypoints.h:401-428) is the reference's own helper; its
 // body becomes this call (same value: see DESIGN.md, F3)
 template <typename PointT>

@@ -260,6 +260,8 @@ _SIGS = {
                                       ctypes.c_int32, ctypes.c_double, ctypes.c_double, c_vp, c_i64, c_i64p, c_vp]),
     "pfx_iss_keypoints": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_int32,
                                   ctypes.c_double, ctypes.c_double, c_vp, c_i64, c_i64p, c_vp]),
+    "pfx_uniform_sampling_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, c_vp, c_i64, c_i64p, c_vp]),
+    "pfx_uniform_sampling": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, c_vp, c_i64, c_i64p, c_vp]),
     "pfx_harris3d_keypoints_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_float,
                                            ctypes.c_int32, ctypes.c_int32, c_vp, c_i64, c_i64p, c_vp, c_vp, c_i64p,
                                            c_vp]),
@@ -288,8 +290,8 @@ _SIGS = {
 
 # entry points an older library loaded through PFX_LIB (A/B runs against a previous build) may lack:
 # test hooks, ICP, spin images, intensity gradients, RIFT, intensity spin images, the shape contexts,
-# moment invariants, principal curvatures, BOARD frames, boundary points, NARF descriptors and the point
-# indices (calling a missing one raises AttributeError there)
+# moment invariants, principal curvatures, BOARD frames, boundary points, NARF descriptors, the point
+# indices and uniform sampling (calling a missing one raises AttributeError there)
 _OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_icp_dev",
                    "pfx_spin_params_default", "pfx_spin_image", "pfx_spin_image_dev",
                    "pfx_intensity_gradient", "pfx_intensity_gradient_dev", "pfx_rift", "pfx_rift_dev",
@@ -301,7 +303,7 @@ _OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_i
                    "pfx_boundary", "pfx_boundary_dev", "pfx_narf_desc_params_default", "pfx_narf_descriptors",
                    "pfx_narf_descriptors_dev", "pfx_point_indices", "pfx_point_indices_dev",
                    "pfx_smooth_clusters", "pfx_smooth_clusters_dev", "pfx_cvfh_params_default", "pfx_cvfh",
-                   "pfx_cvfh_dev"}
+                   "pfx_cvfh_dev", "pfx_uniform_sampling", "pfx_uniform_sampling_dev"}
 
 _lib = None
 

@@ -948,6 +948,29 @@ class Context:
                                                     _ptr(idx), idx.numel(), ctypes.byref(k), _ptr(third)))
         return k.value
 
+    def uniform_sampling(self, x, y, z, radius, return_leaf=False):
+        """UniformSampling::compute (keypoints.h:274-290), host arrays: one keypoint per occupied
+        voxel of edge `radius`, int32 cloud indices in ascending leaf index (and the leaf indices)."""
+        x, y, z = map(_f32, (x, y, z))
+        n = len(x)
+        idx = np.empty(max(n, 1), np.int32)
+        leaf = np.empty(max(n, 1), np.int32) if return_leaf else None
+        k = ctypes.c_int64()
+        self._check(self._lib.pfx_uniform_sampling(self.h, _ptr(x), _ptr(y), _ptr(z), n, radius, _ptr(idx), len(idx),
+                                                   ctypes.byref(k), _ptr(leaf)))
+        out = idx[: k.value].copy()
+        return (out, leaf[: k.value].copy()) if return_leaf else out
+
+    def uniform_sampling_dev(self, x, y, z, radius, idx, leaf=None):
+        """Device version: indices into `idx` (int32 tensor; its size is the capacity) and the leaf
+        indices into `leaf` (int32 tensor of at least that size, optional); returns their number."""
+        if leaf is not None and leaf.numel() < idx.numel():
+            raise ValueError("uniform_sampling_dev: leaf holds fewer elements than idx")
+        k = ctypes.c_int64()
+        self._check(self._lib.pfx_uniform_sampling_dev(self.h, _ptr(x), _ptr(y), _ptr(z), x.numel(), radius,
+                                                       _ptr(idx), idx.numel(), ctypes.byref(k), _ptr(leaf)))
+        return k.value
+
     def harris3d_keypoints(self, x, y, z, radius=0.01, threshold=1e-6, refine=True, non_max=True, details=False):
         """HarrisKeypoint3D + getKeypointsCloud (keypoints.h:150-162, 365-395), host arrays: the
         snapped cloud indices in corner order (details: and the per-point response and the

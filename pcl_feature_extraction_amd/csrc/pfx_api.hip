@@ -1705,6 +1705,41 @@ extern "C" pfx_status pfx_iss_keypoints(pfx_ctx* ctx, const float* x, const floa
   PFX_API_END(ctx)
 }
 
+extern "C" pfx_status pfx_uniform_sampling_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z,
+                                               int64_t n, double radius, int32_t* d_idx, int64_t cap, int64_t* n_out,
+                                               int32_t* d_leaf) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  check_points(d_x, d_y, d_z, n, "uniform_sampling");
+  check_keypoints_out(n_out, cap, d_idx, "uniform_sampling");
+  pfx::uniform_radius_rule(radius);
+  *n_out = 0;
+  const int64_t k = pfx::uniform_sampling_dev(ctx, d_x, d_y, d_z, n, radius, d_idx, cap, d_leaf);
+  *n_out = k;
+  check_capacity(k > cap, "uniform_sampling", k, "keypoints");
+  PFX_API_END(ctx)
+}
+
+extern "C" pfx_status pfx_uniform_sampling(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
+                                           double radius, int32_t* idx, int64_t cap, int64_t* n_out, int32_t* leaf) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  check_points(x, y, z, n, "uniform_sampling");
+  check_keypoints_out(n_out, cap, idx, "uniform_sampling");
+  pfx::uniform_radius_rule(radius);
+  *n_out = 0;
+  const Dev3 d = stage3(ctx, "in_", x, y, z, n);
+  int32_t* di = ctx->buf("out_uniform_idx").as<int32_t>(n + 1);
+  int32_t* dl = leaf ? ctx->buf("out_uniform_leaf").as<int32_t>(n + 1) : nullptr;
+  const int64_t k = pfx::uniform_sampling_dev(ctx, d.x, d.y, d.z, n, radius, di, n, dl);
+  *n_out = k;
+  check_capacity(k > cap, "uniform_sampling", k, "keypoints");
+  rows_out(ctx, idx, di, k, 1);
+  rows_out(ctx, leaf, dl, k, 1);
+  PFX_HIP(hipStreamSynchronize(ctx->stream));
+  PFX_API_END(ctx)
+}
+
 extern "C" pfx_status pfx_harris3d_keypoints_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z,
                                                  int64_t n, double radius, float threshold, int32_t non_max,
                                                  int32_t refine, int32_t* d_idx, int64_t cap, int64_t* n_out,

@@ -328,10 +328,10 @@ __global__ void __launch_bounds__(256) k_fat_cells(const int32_t* __restrict__ c
 }  // namespace
 
 // bounds of the finite points: per-block partials read back once (pinned) and reduced here
-static bool bbox_dev(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const float* d_z, int64_t n,
+static bool bbox_dev(pfx_ctx* ctx, DevBuf& scratch, const float* d_x, const float* d_y, const float* d_z, int64_t n,
                      double lo[3], double hi[3]) {
   hipStream_t st = ctx->stream;
-  uint32_t* mm = g.b_minmax.as<uint32_t>(6 * (kBboxBlocks + 1));
+  uint32_t* mm = scratch.as<uint32_t>(6 * (kBboxBlocks + 1));
   // ~4 points per thread over up to 1,024 workgroups, reduced on the device (one 24-B readback);
   // 128 workgroups of ~30 points per thread took 28 us alone, 160 us beside NARF's range-image
   // projection (headline A/B: 168.0 vs 168.3 Mpoints/s, within noise)
@@ -357,7 +357,12 @@ static bool bbox_dev(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, 
 
 void points_bbox(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const float* d_z, int64_t n,
                  double lo[3], double hi[3]) {
-  bbox_dev(ctx, g, d_x, d_y, d_z, n, lo, hi);
+  bbox_dev(ctx, g.b_minmax, d_x, d_y, d_z, n, lo, hi);
+}
+
+bool points_bbox_any(pfx_ctx* ctx, DevBuf& scratch, const float* d_x, const float* d_y, const float* d_z, int64_t n,
+                     double lo[3], double hi[3]) {
+  return bbox_dev(ctx, scratch, d_x, d_y, d_z, n, lo, hi);
 }
 
 // fork_gather (the normal estimation's opt-in, honoured by hinted radix builds only): the sorted
@@ -390,7 +395,7 @@ void build_grid(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const
     }
     g.oob = g.b_oob.as<int>(1);
   } else if (n > 0) {
-    bbox_dev(ctx, g, d_x, d_y, d_z, n, lo, hi);
+    bbox_dev(ctx, g.b_minmax, d_x, d_y, d_z, n, lo, hi);
     // the hint for the next speculative build: 10 % wider on every side, plus two cells (scans of
     // one sensor keep their extent)
     for (int d = 0; d < 3; ++d) {

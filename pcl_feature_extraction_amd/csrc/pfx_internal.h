@@ -291,6 +291,9 @@ void build_grid(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const
 // bounding box of the finite points (0 when there are none), synchronous
 void points_bbox(pfx_ctx* ctx, Grid& g, const float* d_x, const float* d_y, const float* d_z, int64_t n,
                  double lo[3], double hi[3]);
+// the same pass without a grid: its partials in `scratch`; false when no point is finite
+bool points_bbox_any(pfx_ctx* ctx, DevBuf& scratch, const float* d_x, const float* d_y, const float* d_z, int64_t n,
+                     double lo[3], double hi[3]);
 // the host's read of a speculative build's validation word: a fat cell is remembered on the grid
 inline void note_grid_word(pfx_ctx* ctx, const Grid& g, int word) {
   if (!(word & kGridFatBit)) return;
@@ -329,6 +332,13 @@ int64_t iss_keypoints_dev(pfx_ctx* ctx, const float* x, const float* y, const fl
                           double non_max, int min_nb, double g21, double g32, int32_t* out, int64_t cap,
                           double* third_out);
 void keypoints_release(pfx_ctx* ctx);
+// UniformSampling (pfx_uniform.hip, DESIGN.md "Uniform sampling: the contract"): the number of
+// occupied cells; their winners into out[0..k) and leaf indices into leaf (nullable) when k <= cap,
+// else nothing written.  Two host waits (the bounds, the count); statistics set before it returns.
+// uniform_radius_rule: PFX_ERR_INVALID unless (float)radius and 1.0f / it are finite and > 0.
+void uniform_radius_rule(double radius);
+int64_t uniform_sampling_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, double radius,
+                             int32_t* out, int64_t cap, int32_t* leaf);
 // ICP (pfx_icp.hip): synchronous; ax/ay/az nullable device arrays of ns floats
 struct IcpResult {
   float T[16];

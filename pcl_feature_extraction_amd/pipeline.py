@@ -482,6 +482,13 @@ def keypoints_iss(ctx: Context, x, y, z, idx, third=None) -> int:
                                  threshold32=0.975, third=third)
 
 
+def keypoints_uniform(ctx: Context, x, y, z, idx, radius: float = 0.05) -> int:
+    """Keypoints("UniformSampling").compute (keypoints.h:274-290): UniformSampling<PointXYZRGB>
+    with setRadiusSearch(normal_radius_search_), one keypoint per occupied voxel of that edge.
+    Keypoint cloud indices (ascending leaf index) into `idx`; returns their number."""
+    return ctx.uniform_sampling_dev(x, y, z, radius, idx)
+
+
 def keypoints_harris3d(ctx: Context, x, y, z, idx) -> int:
     """Keypoints("Harris3D").compute (keypoints.h:150-162): HarrisKeypoint3D<PointXYZRGB,
     PointXYZI> with non-maximum suppression, threshold 1e-6, radius 0.01 (the constructor's
