@@ -57,6 +57,9 @@
  *   pfx_point_indices*  <- Tools::getIndices (tools.h:91-102)
  *   pfx_radius_search*  <- search::KdTree<PointXYZRGB>::radiusSearch (features.h:192,
  *                          tools.h:29; FLANN order: (d^2, index) ascending, strict d^2 < r^2)
+ *   pfx_knn_search*     <- KdTreeFLANN<PointXYZRGB>::nearestKSearch (FLANN's KNNSimpleResultSet: the
+ *                          k smallest (d^2, index), self included; exact d^2 ties by index)
+ *   pfx_normals_knn*    <- NormalEstimationOMP<PointXYZRGB,Normal>::compute with setKSearch(k)
  *   pfx_nearest_descriptors_dev <- Features<T>::getCorrespondences (features.h:255-273):
  *                          KdTreeFLANN<FeatureT>::nearestKSearch(k = 1) per descriptor
  *   pfx_correspondences* <- Features<T>::findCorrespondences (features.h:224-253)
@@ -206,6 +209,34 @@ pfx_status pfx_radius_search(pfx_ctx* ctx, const float* x, const float* y, const
                              int64_t nq, double radius, int64_t* counts, int32_t* idx,
                              float* d2, int64_t cap);
 
+/* ---- k-nearest-neighbour search (FLANN semantics; DESIGN.md "k-NN: the contract") ---- */
+/* The largest k of pfx_knn_search* and pfx_normals_knn* (a wave keeps a row and one batch of 64
+ * candidates in its 4 KB of LDS). */
+#define PFX_KNN_MAX_K 256
+/* The surface is the finite points of (x, y, z), m of them; a non-finite point is never a
+ * neighbour (PCL's kd-tree drops them).  A finite query receives the min(k, m) surface points of
+ * smallest key (d2, index) in ascending key order, d2 = ((0 + dx*dx) + dy*dy) + dz*dz in float32,
+ * dx = q - p, no FMA (the radius search's d2): counts[q] = min(k, m), idx / d2 rows of stride k, the
+ * rest of a row idx = -1 and d2 = NaN.  A query that is a surface point finds itself first (d2 = 0),
+ * its duplicates after it in index order.  A non-finite query: counts = 0, the whole row -1 / NaN.
+ * Exact float-d2 ties are broken by index, inside a row and for the k-th place; FLANN breaks them by
+ * the order its kd-tree visits the leaves (the one departure from PCL; DESIGN.md gives its measured
+ * frequency).  The result does not depend on density, extent or launch order.
+ *   PFX_ERR_INVALID   k < 1, a negative count, a null pointer where its side has rows;
+ *   PFX_ERR_CAPACITY  k > PFX_KNN_MAX_K; 2^28 points or queries and more (the neighbour lists'
+ *                     limit).  The outputs are untouched in both cases.
+ * n = 0 (every count 0) and nq = 0 succeed.  Host waits: the bounds, then one per grid searched
+ * (at most 6).  Statistics: "knn_queries" (nq), "knn_rounds" (grids built), and one per path a query
+ * takes: "knn_first" (certified on the first grid), "knn_requeued" (on a later grid of doubled
+ * cell), "knn_exhaustive" (by the scan of every point), "knn_skipped" (non-finite); they sum to nq
+ * when the surface has a finite point. */
+pfx_status pfx_knn_search(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
+                          const float* qx, const float* qy, const float* qz, int64_t nq, int32_t k,
+                          int64_t* counts, int32_t* idx, float* d2);
+pfx_status pfx_knn_search_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z, int64_t n,
+                              const float* d_qx, const float* d_qy, const float* d_qz, int64_t nq, int32_t k,
+                              int64_t* d_counts, int32_t* d_idx, float* d_d2);
+
 /* ---- normals: NormalEstimationOMP (input == surface) ------------------------------- */
 pfx_status pfx_normals(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n,
                        double radius, const float viewpoint[3], float* nx, float* ny, float* nz,
@@ -213,6 +244,17 @@ pfx_status pfx_normals(pfx_ctx* ctx, const float* x, const float* y, const float
 pfx_status pfx_normals_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z,
                            int64_t n, double radius, const float viewpoint[3], float* d_nx,
                            float* d_ny, float* d_nz, float* d_curvature);
+/* NormalEstimationOMP with setKSearch(k), input == surface: point i takes query i's row of
+ * pfx_knn_search (surface = queries = the cloud), and from it the single-pass float covariance in
+ * row order, pcl::eigen33, the curvature and the flip towards the viewpoint (NULL: the origin) --
+ * pfx_normals' arithmetic.  Fewer than 3 neighbours (so k = 1, k = 2, or a cloud of fewer than 3
+ * finite points) and non-finite points give four NaNs, as PCL.  k, its errors and the statistics are
+ * pfx_knn_search's. */
+pfx_status pfx_normals_knn(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, int32_t k,
+                           const float viewpoint[3], float* nx, float* ny, float* nz, float* curvature);
+pfx_status pfx_normals_knn_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z, int64_t n,
+                               int32_t k, const float viewpoint[3], float* d_nx, float* d_ny, float* d_nz,
+                               float* d_curvature);
 /* The same computation in two phases, so that a caller can order the points it needs first
  * (results identical to pfx_normals_dev):
  *   lists  -- radius-neighbour lists of every finite point, kept in ctx; outputs NaN-filled;

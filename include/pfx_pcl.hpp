@@ -346,6 +346,17 @@ class Feature {
       PCL_ERROR("%s\n", k_search_error_.c_str());
       return;
     }
+    if (accepts_k_search_ && k_ != 0 && input_ && !input_->empty()) {
+      // PCL's initCompute rule for the class that opted in: one of the two, never both
+      if (search_radius_ != 0.0) {
+        PCL_ERROR("[pcl::%s::compute] Both radius (%f) and K (%d) defined! Set one of them to zero first and then "
+                  "re-run compute ().\n", name_.c_str(), search_radius_, k_);
+        return;
+      }
+      if (!detail::context()) return;
+      computeFeature(output);
+      return;
+    }
     if (!input_ || input_->empty() || k_ != 0 || !(search_radius_ > 0.0)) {
       PCL_ERROR("[pcl::%s::compute] initCompute failed (needs an input cloud and a radius; "
                 "k-NN search is not on the accelerated path)\n", name_.c_str());
@@ -369,6 +380,7 @@ class Feature {
   }
   std::string name_ = "Feature";
   std::string k_search_error_;  // a class whose PCL original refuses a k-search in its own words sets them
+  bool accepts_k_search_ = false;  // a class with a k-NN path sets it: k_ != 0 and radius 0 reach computeFeature
   PointCloudInConstPtr input_, surface_;
   KdTreePtr tree_;
   double search_radius_ = 0.0;
@@ -392,11 +404,15 @@ class FeatureFromNormals : public Feature<PointInT, PointOutT> {
   PointCloudNConstPtr normals_;
 };
 
-// NormalEstimationOMP<In, Normal> (tools.h:22-32): viewpoint (0,0,0) unless set
+// NormalEstimationOMP<In, Normal> (tools.h:22-32): viewpoint (0,0,0) unless set.  setRadiusSearch(r) runs
+// pfx_normals, setKSearch(k) with radius 0 pfx_normals_knn (1 <= k <= PFX_KNN_MAX_K); both set is PCL's error.
 template <typename PointInT, typename PointOutT>
 class NormalEstimationOMP : public Feature<PointInT, PointOutT> {
  public:
-  explicit NormalEstimationOMP(unsigned int /*nr_threads*/ = 0) { this->name_ = "NormalEstimationOMP"; }
+  explicit NormalEstimationOMP(unsigned int /*nr_threads*/ = 0) {
+    this->name_ = "NormalEstimationOMP";
+    this->accepts_k_search_ = true;
+  }
   void setViewPoint(float vx, float vy, float vz) { vp_[0] = vx; vp_[1] = vy; vp_[2] = vz; }
   void setNumberOfThreads(unsigned int) {}
 
@@ -411,10 +427,12 @@ class NormalEstimationOMP : public Feature<PointInT, PointOutT> {
     const detail::SoA s = detail::soa_xyz(in);
     const size_t n = in.size();
     std::vector<float> nx(n), ny(n), nz(n), cv(n);
-    if (!detail::ok(pfx_normals(detail::context(), s.x.data(), s.y.data(), s.z.data(), (int64_t)n,
-                                this->search_radius_, vp_, nx.data(), ny.data(), nz.data(), cv.data()),
-                    "NormalEstimationOMP"))
-      return;
+    const pfx_status st =
+        this->k_ != 0 ? pfx_normals_knn(detail::context(), s.x.data(), s.y.data(), s.z.data(), (int64_t)n, this->k_, vp_,
+                                        nx.data(), ny.data(), nz.data(), cv.data())
+                      : pfx_normals(detail::context(), s.x.data(), s.y.data(), s.z.data(), (int64_t)n,
+                                    this->search_radius_, vp_, nx.data(), ny.data(), nz.data(), cv.data());
+    if (!detail::ok(st, "NormalEstimationOMP")) return;
     out.resize(n);
     out.is_dense = true;
     for (size_t i = 0; i < n; ++i) {
@@ -1681,7 +1699,9 @@ class KdTreeFLANN {
 
 // KdTreeFLANN over a point cloud (Keypoints::getKeypointsCloud, keypoints.h:374-392): exact
 // nearestKSearch(k = 1) as radius searches on the GPU (pfx_radius_search) over a growing ball --
-// the first non-empty ball holds the nearest point, the first entry of FLANN's (d2, index) order
+// the first non-empty ball holds the nearest point, the first entry of FLANN's (d2, index) order.
+// 2 <= k <= PFX_KNN_MAX_K: pfx_knn_search, the min(k, finite points) smallest (d2, index) in that
+// order (exact d2 ties by index, DESIGN.md "k-NN: the contract"); returns their number.
 template <>
 class KdTreeFLANN<PointXYZRGB> {
  public:
@@ -1703,14 +1723,27 @@ class KdTreeFLANN<PointXYZRGB> {
                      std::vector<float>& k_sqr_distances) const {
     k_indices.clear();
     k_sqr_distances.clear();
-    if (k != 1 || !target_ || soa_.x.empty()) {
-      if (k != 1) PCL_ERROR("[pcl::KdTreeFLANN::nearestKSearch] only k = 1 is accelerated\n");
+    if (k < 1 || k > PFX_KNN_MAX_K || !target_ || soa_.x.empty()) {
+      if (k < 1 || k > PFX_KNN_MAX_K)
+        PCL_ERROR("[pcl::KdTreeFLANN::nearestKSearch] k must be in [1, %d]\n", PFX_KNN_MAX_K);
       return 0;
     }
     if (!(std::isfinite(point.x) && std::isfinite(point.y) && std::isfinite(point.z)) || !detail::context())
       return 0;
     std::lock_guard<std::mutex> lock(detail::context_mutex());
     const float qx = point.x, qy = point.y, qz = point.z;
+    if (k > 1) {
+      int64_t cnt = 0;
+      std::vector<int32_t> idx(k);
+      std::vector<float> d2(k);
+      if (!detail::ok(pfx_knn_search(detail::context(), soa_.x.data(), soa_.y.data(), soa_.z.data(),
+                                     (int64_t)soa_.x.size(), &qx, &qy, &qz, 1, k, &cnt, idx.data(), d2.data()),
+                      "KdTreeFLANN"))
+        return 0;
+      k_indices.assign(idx.begin(), idx.begin() + cnt);
+      k_sqr_distances.assign(d2.begin(), d2.begin() + cnt);
+      return (int)cnt;
+    }
     // the ball must reach the farthest point of the cloud's box: its diagonal from any point in it
     const double limit = 4.0 * (extent_ + std::fabs((double)qx) + std::fabs((double)qy) + std::fabs((double)qz)) + 1.0;
     for (double r = 0.01; r <= limit; r *= 4.0) {

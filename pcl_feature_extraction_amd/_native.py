@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("PFX_LIB") or os.path.join(_HERE, "libpfx.so")
 
 PFX_OK, PFX_ERR_INVALID, PFX_ERR_DEVICE, PFX_ERR_CAPACITY, PFX_ERR_UNSUPPORTED = 0, 1, 2, 3, 4
 BOUNDARY_NO_NEIGHBORS = 255   # PFX_BOUNDARY_NO_NEIGHBORS: a row of pfx_boundary without a neighbour
+KNN_MAX_K = 256               # PFX_KNN_MAX_K: the largest k of pfx_knn_search* and pfx_normals_knn*
 _ERRNAMES = {1: "PFX_ERR_INVALID", 2: "PFX_ERR_DEVICE", 3: "PFX_ERR_CAPACITY", 4: "PFX_ERR_UNSUPPORTED"}
 
 c_f32p = ctypes.POINTER(ctypes.c_float)
@@ -260,6 +261,12 @@ _SIGS = {
                                       ctypes.c_int32, ctypes.c_double, ctypes.c_double, c_vp, c_i64, c_i64p, c_vp]),
     "pfx_iss_keypoints": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_int32,
                                   ctypes.c_double, ctypes.c_double, c_vp, c_i64, c_i64p, c_vp]),
+    "pfx_knn_search": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, ctypes.c_int32, c_vp, c_vp,
+                               c_vp]),
+    "pfx_knn_search_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, ctypes.c_int32, c_vp,
+                                   c_vp, c_vp]),
+    "pfx_normals_knn": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "pfx_normals_knn_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pfx_uniform_sampling_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, c_vp, c_i64, c_i64p, c_vp]),
     "pfx_uniform_sampling": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, c_vp, c_i64, c_i64p, c_vp]),
     "pfx_harris3d_keypoints_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_float,
@@ -291,7 +298,7 @@ _SIGS = {
 # entry points an older library loaded through PFX_LIB (A/B runs against a previous build) may lack:
 # test hooks, ICP, spin images, intensity gradients, RIFT, intensity spin images, the shape contexts,
 # moment invariants, principal curvatures, BOARD frames, boundary points, NARF descriptors, the point
-# indices and uniform sampling (calling a missing one raises AttributeError there)
+# indices, uniform sampling and the k-NN calls (calling a missing one raises AttributeError there)
 _OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_icp_dev",
                    "pfx_spin_params_default", "pfx_spin_image", "pfx_spin_image_dev",
                    "pfx_intensity_gradient", "pfx_intensity_gradient_dev", "pfx_rift", "pfx_rift_dev",
@@ -303,7 +310,8 @@ _OLDER_MAY_LACK = {"pfx_grid_debug", "pfx_icp_params_default", "pfx_icp", "pfx_i
                    "pfx_boundary", "pfx_boundary_dev", "pfx_narf_desc_params_default", "pfx_narf_descriptors",
                    "pfx_narf_descriptors_dev", "pfx_point_indices", "pfx_point_indices_dev",
                    "pfx_smooth_clusters", "pfx_smooth_clusters_dev", "pfx_cvfh_params_default", "pfx_cvfh",
-                   "pfx_cvfh_dev", "pfx_uniform_sampling", "pfx_uniform_sampling_dev"}
+                   "pfx_cvfh_dev", "pfx_uniform_sampling", "pfx_uniform_sampling_dev", "pfx_knn_search",
+                   "pfx_knn_search_dev", "pfx_normals_knn", "pfx_normals_knn_dev"}
 
 _lib = None
 

@@ -242,6 +242,29 @@ class Context:
                                                 int(cap)))
         return counts, idx, d2
 
+    def knn_search(self, x, y, z, qx, qy, qz, k):
+        """KdTreeFLANN::nearestKSearch (pfx_knn_search), host arrays: (counts (nq,) int64, idx (nq, k)
+        int32, d2 (nq, k) float32); each row the min(k, finite points) smallest (d2, index) ascending,
+        then -1 / NaN."""
+        x, y, z, qx, qy, qz = map(_f32, (x, y, z, qx, qy, qz))
+        nq, k = len(qx), int(k)
+        counts = np.zeros(nq, dtype=np.int64)
+        idx = np.full((nq, max(k, 1)), -1, dtype=np.int32)
+        d2 = np.full((nq, max(k, 1)), np.nan, dtype=np.float32)
+        self._check(self._lib.pfx_knn_search(self.h, _ptr(x), _ptr(y), _ptr(z), len(x), _ptr(qx), _ptr(qy), _ptr(qz),
+                                             nq, k, _ptr(counts), _ptr(idx), _ptr(d2)))
+        return counts, idx, d2
+
+    def normals_knn(self, x, y, z, k, viewpoint=(0.0, 0.0, 0.0)):
+        """NormalEstimationOMP with setKSearch(k) (pfx_normals_knn), host arrays."""
+        x, y, z = map(_f32, (x, y, z))
+        n = len(x)
+        out = np.empty((4, n), dtype=np.float32)
+        vp = _f32(viewpoint)
+        self._check(self._lib.pfx_normals_knn(self.h, _ptr(x), _ptr(y), _ptr(z), n, int(k), _ptr(vp), _ptr(out[0]),
+                                              _ptr(out[1]), _ptr(out[2]), _ptr(out[3])))
+        return out[0], out[1], out[2], out[3]
+
     def normals(self, x, y, z, r, viewpoint=(0.0, 0.0, 0.0)):
         x, y, z = map(_f32, (x, y, z))
         n = len(x)
@@ -592,6 +615,19 @@ class Context:
         vp = _f32(viewpoint)
         self._check(self._lib.pfx_normals_dev(self.h, _ptr(x), _ptr(y), _ptr(z), x.numel(), float(r), _ptr(vp),
                                               _ptr(nx), _ptr(ny), _ptr(nz), _ptr(curv)))
+
+    def knn_search_dev(self, x, y, z, qx, qy, qz, k, counts, idx, d2):
+        """Device version: counts (nq,) int64, idx (nq, k) int32 and d2 (nq, k) float32 tensors."""
+        nq, k = qx.numel(), int(k)
+        if counts.numel() < nq or idx.numel() < nq * k or d2.numel() < nq * k:
+            raise ValueError("knn_search_dev: an output holds fewer than nq rows of k")
+        self._check(self._lib.pfx_knn_search_dev(self.h, _ptr(x), _ptr(y), _ptr(z), x.numel(), _ptr(qx), _ptr(qy),
+                                                 _ptr(qz), nq, k, _ptr(counts), _ptr(idx), _ptr(d2)))
+
+    def normals_knn_dev(self, x, y, z, k, nx, ny, nz, curv, viewpoint=(0.0, 0.0, 0.0)):
+        vp = _f32(viewpoint)
+        self._check(self._lib.pfx_normals_knn_dev(self.h, _ptr(x), _ptr(y), _ptr(z), x.numel(), int(k), _ptr(vp),
+                                                  _ptr(nx), _ptr(ny), _ptr(nz), _ptr(curv)))
 
     def normals_fast_dev(self, x, y, z, r, nx, ny, nz, curv, viewpoint=(0.0, 0.0, 0.0)):
         vp = _f32(viewpoint)

@@ -373,6 +373,69 @@ pfx_status pfx_radius_search(pfx_ctx* ctx, const float* x, const float* y, const
   PFX_API_END(ctx)
 }
 
+static void knn_rule(In3 s, int64_t n, In3 q, int64_t nq, int32_t k, const int64_t* counts, const int32_t* idx,
+                     const float* d2) {
+  args_rule("knn_search", n, all_set(s), nq, all_set(q, counts, idx, d2));
+  pfx::knn_k_rule(k, "knn_search");
+  pfx::knn_count_rule(n, nq, "knn_search");
+}
+
+pfx_status pfx_knn_search_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z, int64_t n,
+                              const float* d_qx, const float* d_qy, const float* d_qz, int64_t nq, int32_t k,
+                              int64_t* d_counts, int32_t* d_idx, float* d_d2) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  knn_rule({d_x, d_y, d_z}, n, {d_qx, d_qy, d_qz}, nq, k, d_counts, d_idx, d_d2);
+  pfx::knn_search_dev(ctx, d_x, d_y, d_z, n, d_qx, d_qy, d_qz, nq, k, d_counts, d_idx, d_d2);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_knn_search(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, const float* qx,
+                          const float* qy, const float* qz, int64_t nq, int32_t k, int64_t* counts, int32_t* idx,
+                          float* d2) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  knn_rule({x, y, z}, n, {qx, qy, qz}, nq, k, counts, idx, d2);
+  const Dev3 s = stage3(ctx, "in_", x, y, z, n), q = stage3(ctx, "in_q", qx, qy, qz, nq);
+  int64_t* dc = ctx->buf("out_counts").as<int64_t>(nq + 1);
+  int32_t* di = ctx->buf("out_idx").as<int32_t>(nq * k + 1);
+  float* dd = ctx->buf("out_d2").as<float>(nq * k + 1);
+  pfx::knn_search_dev(ctx, s.x, s.y, s.z, n, q.x, q.y, q.z, nq, k, dc, di, dd);
+  finish_host(ctx, nq, {{counts, dc, 1}, {idx, di, k}, {d2, dd, k}});
+  PFX_API_END(ctx)
+}
+
+static void normals_knn_rule(In3 p, int64_t n, int32_t k, const float* nx, const float* ny, const float* nz,
+                             const float* curvature) {
+  args_rule("normals_knn", n, all_set(p, nx, ny, nz, curvature), 0, true);
+  pfx::knn_k_rule(k, "normals_knn");
+  pfx::knn_count_rule(n, 0, "normals_knn");
+}
+
+pfx_status pfx_normals_knn_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z, int64_t n,
+                               int32_t k, const float viewpoint[3], float* d_nx, float* d_ny, float* d_nz,
+                               float* d_curvature) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  normals_knn_rule({d_x, d_y, d_z}, n, k, d_nx, d_ny, d_nz, d_curvature);
+  const float vp0[3] = {0.f, 0.f, 0.f};
+  pfx::normals_knn_dev(ctx, d_x, d_y, d_z, n, k, viewpoint ? viewpoint : vp0, d_nx, d_ny, d_nz, d_curvature);
+  PFX_API_END(ctx)
+}
+
+pfx_status pfx_normals_knn(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, int32_t k,
+                           const float viewpoint[3], float* nx, float* ny, float* nz, float* curvature) {
+  PFX_API_BEGIN
+  check_ctx(ctx);
+  normals_knn_rule({x, y, z}, n, k, nx, ny, nz, curvature);
+  const Dev3 d = stage3(ctx, "in_", x, y, z, n);
+  float* o = ctx->buf("out_normals").as<float>(4 * n + 4);
+  const float vp0[3] = {0.f, 0.f, 0.f};
+  pfx::normals_knn_dev(ctx, d.x, d.y, d.z, n, k, viewpoint ? viewpoint : vp0, o, o + n, o + 2 * n, o + 3 * n);
+  finish_host(ctx, n, {{nx, o, 1}, {ny, o + n, 1}, {nz, o + 2 * n, 1}, {curvature, o + 3 * n, 1}});
+  PFX_API_END(ctx)
+}
+
 pfx_status pfx_normals_dev(pfx_ctx* ctx, const float* d_x, const float* d_y, const float* d_z, int64_t n,
                            double radius, const float viewpoint[3], float* d_nx, float* d_ny, float* d_nz,
                            float* d_curvature) {

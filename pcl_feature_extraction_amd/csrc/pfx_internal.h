@@ -339,6 +339,18 @@ void keypoints_release(pfx_ctx* ctx);
 void uniform_radius_rule(double radius);
 int64_t uniform_sampling_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, double radius,
                              int32_t* out, int64_t cap, int32_t* leaf);
+// k-NN (pfx_knn.hip, DESIGN.md "k-NN: the contract"): synchronous (one host wait per grid searched);
+// statistics set before it returns.  d2 nullable; fill_rows: the rows' padding (-1 / NaN) is written,
+// else only counts says how much of a row holds.  knn_k_rule: PFX_ERR_INVALID for k < 1,
+// PFX_ERR_CAPACITY beyond PFX_KNN_MAX_K; knn_count_rule: PFX_ERR_CAPACITY for 2^28 points or queries
+// and more (the neighbour lists' limit).  Both calls build ctx->grid_b.
+void knn_k_rule(int32_t k, const char* what);
+void knn_count_rule(int64_t n, int64_t nq, const char* what);
+void knn_search_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, const float* qx,
+                    const float* qy, const float* qz, int64_t nq, int32_t k, int64_t* counts, int32_t* idx,
+                    float* d2, bool fill_rows = true);
+void normals_knn_dev(pfx_ctx* ctx, const float* x, const float* y, const float* z, int64_t n, int32_t k,
+                     const float vp[3], float* nx, float* ny, float* nz, float* curv);
 // ICP (pfx_icp.hip): synchronous; ax/ay/az nullable device arrays of ns floats
 struct IcpResult {
   float T[16];
